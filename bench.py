@@ -11,7 +11,9 @@ run N independent shards with no data-path collective (weak scaling); value = al
 Other configurations of BASELINE.json (--config): c3 = same grid, bf16 matrix products, batch 16; c4 = global batch 64 sharded
 over the ranks (8 per GPU at N = 8; strong scaling); c5 = 0.25 degree grid, mesh resolution 3, batch 1.
 
-Prints ONE JSON line with the driver contract fields plus
+A plain run sets up, runs W untimed and K timed steps, writes the last timed step's outputs when --dump-outputs DIR is
+given (DIR/<name>.npy, float32; inputs and weights are seeded, so two builds can be compared output for output) and
+prints ONE JSON line with the driver contract fields.  Everything else is measured only with --full, which adds
   "roofline":     the dominant kernel (decoder edge update): EXECUTED matrix FLOPs per launch / HIP-event duration against the
                   MFMA peak of the arithmetic dtype (frac <= 1); the figure on the reference's algorithmic FLOPs (which the
                   layer-1 split legally does not execute) is kept under algorithmic_*; step_frac = the whole forward;
@@ -20,6 +22,7 @@ Prints ONE JSON line with the driver contract fields plus
   "extra":        c3 and c5 measured in the same run (N = 1 only), each with value, ms_per_step and its dominant kernel;
   "cpu_baseline": the CPU oracle (port of the reference forward) on this host: batch 2, 1 warm-up + 3 timed forwards, mean
                   and min, replicated-graph semantics (what the reference executes) with the shared-graph variant beside it.
+Without --full these keys are present and null (roofline, kernel_timer_pass_ms_per_step, cpu_baseline) or absent.
 """
 from __future__ import annotations
 
@@ -113,7 +116,9 @@ def cpu_baseline(lat_lons, state, graphs):
     g = graphs.as_oracle_dict()
     ncpu = os.cpu_count() or 1
     default_threads = torch.get_num_threads()
-    threads = max(1, min(32, ncpu))
+    # a host that grants this process fewer CPUs than it has says so in OMP_NUM_THREADS: neither variant uses more
+    limit = int(os.environ["OMP_NUM_THREADS"]) if os.environ.get("OMP_NUM_THREADS", "").isdigit() else 64
+    threads = max(1, min(32, ncpu, limit))
 
     def timed(shared, n=3):
         om.forecaster_forward(state, g, feats, shared=shared)  # warm-up
@@ -136,7 +141,7 @@ def cpu_baseline(lat_lons, state, graphs):
             old = os.sched_getaffinity(0)
             try:
                 os.sched_setaffinity(0, set(cpus) & old or old)
-                st = max(1, min(64, len(set(cpus) & old) // 2 or 1))
+                st = max(1, min(64, limit, len(set(cpus) & old) // 2 or 1))
                 torch.set_num_threads(st)
                 ts = timed(False)
                 socket = {"threads": st, "logical_cpus_of_socket": len(cpus), "seconds": ts, "value": 2.0 / (sum(ts) / len(ts)),
@@ -236,14 +241,16 @@ def build_model(cfg, dev):
     return model, lat_lons
 
 
-DEFAULT_PATH_NOTE = ("model(features) in eval() under torch.no_grad(), as a caller writes it: from the third call of a shape on "
-                     "graph_weather_amd replays the forward from one HIP graph (graphed.AutoGraph; same kernels, same arguments, "
-                     "output cloned); kernel durations are HIP-event timed in a separate eager pass of the same process")
+PATH_NOTE = ("model(features) in eval() under torch.no_grad(), as a caller writes it: from the third call of a shape on "
+             "graph_weather_amd replays the forward from one HIP graph (graphed.AutoGraph; same kernels, same arguments, "
+             "output cloned)")
+DEFAULT_PATH_NOTE = PATH_NOTE + "; kernel durations are HIP-event timed in a separate eager pass of the same process"
 
 
-def time_forward(model, feats, steps, warmup, barrier, kernel_timer=True):
+def time_forward(model, feats, steps, warmup, barrier, kernel_timer=True, outputs=None):
     """W untimed steps, then exactly K steps between barrier + synchronise.  ``kernel_timer``: HIP events around the tagged edge
-    launches (an active timer keeps every call eager: events cannot be recorded into a HIP graph)."""
+    launches (an active timer keeps every call eager: events cannot be recorded into a HIP graph).  ``outputs``: a dict that
+    receives the last timed step's forecast under "forecast"."""
     from graph_weather_amd import ops
 
     with torch.no_grad():
@@ -258,7 +265,35 @@ def time_forward(model, feats, steps, warmup, barrier, kernel_timer=True):
         elapsed = time.perf_counter() - t0
     timer, ops.TIMER = ops.TIMER, None
     assert torch.isfinite(y).all()
+    if outputs is not None:
+        outputs["forecast"] = y
     return elapsed, timer
+
+
+DUMP_BUDGET_BYTES = 60 * 2**20  # files and headers together stay below 64 MB
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write each tensor of ``arrays`` as ``out_dir/<name>.npy`` (float64 stays float64, everything else becomes float32).  When
+    the arrays together exceed ``budget`` bytes, the budget is shared out smallest array first, and an array larger than its
+    share keeps a fixed, seeded sample of its rows (last dimension kept whole, rows in ascending order): the same sample for the
+    same shapes, so two runs compare element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach() for k, v in arrays.items()}
+    size = lambda t: t.numel() * (8 if t.dtype == torch.float64 else 4)  # noqa: E731
+    left = budget
+    for i, name in enumerate(sorted(arrays, key=lambda k: (size(arrays[k]), k))):
+        t = arrays[name]
+        share = left // (len(arrays) - i)
+        left -= min(size(t), share)
+        if size(t) > share:
+            rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+            keep = max(1, share // max(1, size(rows[0])))
+            idx = np.sort(np.random.default_rng(seed).choice(rows.shape[0], size=keep, replace=False))
+            t = rows[torch.from_numpy(idx).to(rows.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), (t if t.dtype == torch.float64 else t.float()).cpu().numpy())
 
 
 def cold_step_ms(model, feats, n=3):
@@ -599,11 +634,16 @@ def train_bench(args, cfg, batch, model, feats, lat_lons, dev, world, rank, back
     else:
         crit = train_factories[0](lat_lons)
         opt = train_factories[1](model.parameters(), flat)
-    target = torch.randn(batch, len(lat_lons), 78, device=dev)
+    # seeded like the features, so that --dump-outputs of two runs compare
+    target = torch.randn(batch, len(lat_lons), 78, generator=torch.Generator().manual_seed(1234 + rank)).to(dev)
+    last = {}
 
     def step():
         flat.zero_()
-        loss = crit(model(feats), target)
+        y = model(feats)
+        if args.dump_outputs:
+            last["forecast"] = y
+        loss = crit(y, target)
         loss.backward()
         flat.allreduce(ctx)
         opt.step()
@@ -618,6 +658,9 @@ def train_bench(args, cfg, batch, model, feats, lat_lons, dev, world, rank, back
     sh.barrier(ctx, dev)
     elapsed = sh.max_over_ranks(ctx, time.perf_counter() - t0, dev)
     assert torch.isfinite(loss)
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, {"forecast": last["forecast"], "loss": loss.reshape(1)}, world, rank)
+    del last
     total = sh.sum_over_ranks(ctx, batch, dev)
     if rank == 0:
         print(json.dumps({
@@ -680,6 +723,14 @@ def run_train_extra(dev, steps=5, warmup=2, precision="fp32"):
     gc.collect()
     torch.cuda.empty_cache()
     return out
+
+
+def write_dump(out_dir, arrays, world, rank):
+    """--dump-outputs: one set of files per process; under several ranks each writes <name>_rank<r>.npy within its share of the
+    64 MB budget."""
+    if world > 1:
+        arrays = {f"{k}_rank{rank}": v for k, v in arrays.items()}
+    dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES // max(1, world))
 
 
 def _rank_entry(rank, world, rendezvous, argv, backend, device, model_factory, train_factories):
@@ -760,8 +811,14 @@ def main(argv=None, backend="nccl", device=None, model_factory=None, train_facto
                     help="forward = BASELINE metric (default); train = forward + loss + backward + gradient all-reduce + AdamW")
     ap.add_argument("--streams", type=int, default=0, help="HIP streams of the mesh stack in the forward (0 = automatic: per-sample "
                                                            "chains on 2 streams for fp32 and batch >= 2; 1 = one stream)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the c3 / c5 measurements and the cold-cache step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the per-kernel roofline passes, the cold-cache step, "
+                         "eager / graph / host-copy figures, the other configurations (extra) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32; at most 64 MB in all, "
+                         "a fixed seeded sample of rows beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the c3 / c5 measurements and the cold-cache step")
     args = ap.parse_args(argv)
 
     from graph_weather_amd import sharding as sh
@@ -805,7 +862,7 @@ def main(argv=None, backend="nccl", device=None, model_factory=None, train_facto
     else:
         batch = cfg["batch"] if args.batch is None else args.batch
     model, lat_lons = (model_factory or build_model)(cfg, dev)
-    cpu_state = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 else None
+    cpu_state = {k: v.clone() for k, v in model.state_dict().items()} if rank == 0 and args.full else None
     graphs = model.encoder.graphs
     model = model.to(dev).eval()
     if cfg["precision"] != "fp32":
@@ -830,10 +887,14 @@ def main(argv=None, backend="nccl", device=None, model_factory=None, train_facto
     gc.collect()
     gc.freeze()
     # The timed region is model(features) as a caller writes it (from the third call on a HIP-graph replay, DEFAULT_PATH_NOTE);
-    # the per-kernel HIP events need eager launches: a separate pass right after it, in this process, on rank 0.
-    elapsed, timer = time_forward(model, feats, args.steps, args.warmup, barrier, kernel_timer=False)
+    # the per-kernel HIP events need eager launches: a separate pass right after it (--full), in this process, on rank 0.
+    last = {}
+    elapsed, timer = time_forward(model, feats, args.steps, args.warmup, barrier, kernel_timer=False, outputs=last)
+    if args.dump_outputs:
+        write_dump(args.dump_outputs, last, world, rank)
+    del last
     timer_pass_ms = None
-    if on_gpu and rank == 0:
+    if args.full and on_gpu and rank == 0:
         # a second timed region of the same K steps, same bracket, with HIP events on the stream each edge launch runs on
         t_el, timer = time_forward(model, feats, args.steps, 1, torch.cuda.synchronize)
         timer_pass_ms = 1e3 * t_el / args.steps
@@ -842,7 +903,7 @@ def main(argv=None, backend="nccl", device=None, model_factory=None, train_facto
     # (5 extra steps outside the timed region) so that bytes / FLOPs / duration belong to the same launch.
     stanza_timer = None
     gp = getattr(getattr(model, "processor", None), "graph_processor", None)
-    if on_gpu and rank == 0 and gp is not None and gp.forward_streams(batch) > 1:
+    if args.full and on_gpu and rank == 0 and gp is not None and gp.forward_streams(batch) > 1:
         keep = gp.streams
         gp.streams = 1
         _, stanza_timer = time_forward(model, feats, 5, 1, torch.cuda.synchronize)
@@ -883,16 +944,16 @@ def main(argv=None, backend="nccl", device=None, model_factory=None, train_facto
             "config": {"workload": f"{args.config}: GraphWeatherForecaster {cfg['grid']:g}deg grid ({len(lat_lons)} nodes), 102->78 feat, "
                                    f"batch={batch} on rank 0, {prec}, mesh res {cfg['resolution']} ({graphs.num_mesh} nodes), random-init weights",
                        "global_batch": total_batch, "parallelism": f"batch-sharded x{world}, no collective in forward"},
-            "roofline": roof, "path": DEFAULT_PATH_NOTE if on_gpu else None,
+            "roofline": roof, "path": (DEFAULT_PATH_NOTE if args.full else PATH_NOTE) if on_gpu else None,
             "kernel_timer_pass_ms_per_step": timer_pass_ms,  # the K-step region the roofline's launch durations were HIP-event timed in
             "algorithmic_gflop_per_forecast": algorithmic_flops_per_forecast(graphs) / 1e9,
             "per_rank_ms_per_step": per_rank_ms, "dist_world_size": dist_world,
         }
-        if world == 1 and not args.no_extra and on_gpu:
+        if args.full and world == 1 and not args.no_extra and on_gpu:
             out["cold_ms_per_step"] = cold_step_ms(model, feats)
             out["cold_note"] = ("forward right after every parameter changed: packed weights, edge / mesh embeddings and their layer-1 "
                                 "products are rebuilt (the reference recomputes the embeddings on every forward)")
-        if world == 1 and not args.no_extra and args.config == "c2" and on_gpu:
+        if args.full and world == 1 and not args.no_extra and args.config == "c2" and on_gpu:
             out["eager"] = eager_ms(model, feats, steps=args.steps)
             out["graph"] = graph_replay_ms(model, feats, steps=args.steps)
             h2d = h2d_step_ms(model, feats)
@@ -908,7 +969,7 @@ def main(argv=None, backend="nccl", device=None, model_factory=None, train_facto
                             "h2d": h2d, "c4_per_gpu": c4_per_gpu(dev)}
             out["extra"]["c3"]["status"] = ("plain bf16 operands: OUTSIDE the 1e-3 parity bar (parity_vs_fp32_kernels); a frozen budget "
                                             "mode - kernels unchanged since round 4, no new work is routed through it")
-        if world == 1 and not args.no_cpu_baseline and cfg["grid"] == 1.0:
+        if args.full and world == 1 and not args.no_cpu_baseline and cfg["grid"] == 1.0:
             out["cpu_baseline"] = cpu_baseline(lat_lons, cpu_state, graphs)
         else:
             out["cpu_baseline"] = None

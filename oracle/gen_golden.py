@@ -169,6 +169,65 @@ def regional_case(ns):
     print("regional_eu_b2", tuple(y.shape), float(y.abs().mean()), float((y - y_nudged).abs().mean()), len(h3_idx))
 
 
+def builder_regions():
+    """The three regions of the DynamicGraphBuilder comparison (tests/test_dynamic_graphs.py): a 5 x 5 block over western Europe,
+    300 seeded points over the globe, the two poles and the origin."""
+    rs = np.random.RandomState(5)
+    return [[(float(lat), float(lon)) for lat in range(50, 55) for lon in range(-2, 3)],
+            [(float(a), float(b)) for a, b in zip(rs.uniform(-90, 90, 300), rs.uniform(-180, 180, 300))],
+            [(-90.0, 0.0), (90.0, 180.0), (0.0, 0.0)]]
+
+
+def _sha256(t):
+    import hashlib
+
+    return hashlib.sha256(t.detach().contiguous().numpy().tobytes()).hexdigest()
+
+
+def live_reference_cases(ns):
+    """What the CPU tests that once ran the reference's own classes compare against, recorded: the 30 degree forecaster
+    (graphs, per-key digests of its seeded weights, output; tests/test_oracle.py), the key -> shape tables of its
+    GraphWeatherForecaster / GraphCast / RegionalForecaster state_dicts (tests/test_alias.py, tests/test_dynamic_graphs.py) and
+    the arrays of its DynamicGraphBuilder on three regions (tests/test_dynamic_graphs.py: ``builder_regions``)."""
+    import json
+
+    lat_lons = regular_lat_lons(30.0)
+    model = ns.GraphWeatherForecaster(lat_lons)
+    deterministic_fill_(model, seed=5)
+    model.eval()
+    feats = seeded_features(3, len(lat_lons), seed=9)
+    with torch.no_grad():
+        y = model(feats)
+    sd = model.state_dict()
+    keys = sorted(sd)
+    np.savez_compressed(os.path.join(OUT, "forecaster_30deg_b3.npz"), y=y.numpy(),
+                        enc_edge_index=model.encoder.graph.edge_index.numpy(),
+                        lat_edge_index=model.encoder.latent_graph.edge_index.numpy(),
+                        dec_edge_index=model.decoder.graph.edge_index.numpy(), dec_edge_attr=model.decoder.graph.edge_attr.numpy(),
+                        state_keys=np.array(keys), state_sha256=np.array([_sha256(sd[k]) for k in keys]))
+    print("forecaster_30deg_b3", tuple(y.shape), float(y.abs().mean()))
+
+    shapes = lambda m: {k: list(v.shape) for k, v in m.state_dict().items()}  # noqa: E731
+    tables = {"GraphWeatherForecaster(regular_lat_lons(30.0))": shapes(model),
+              "GraphCast(regular_lat_lons(30.0))": shapes(ns.GraphCast(lat_lons)),
+              "RegionalForecasterConfig(enable_nudging=True).build()": shapes(ns.RegionalForecasterConfig(enable_nudging=True).build())}
+    with open(os.path.join(OUT, "reference_state_dict_shapes.json"), "w") as fh:
+        json.dump(tables, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+    print("reference_state_dict_shapes", {k: len(v) for k, v in tables.items()})
+
+    builder = ns.DynamicGraphBuilder(resolution=2)
+    arrays = {}
+    for i, region in enumerate(builder_regions()):
+        r = builder(region)
+        for j, g in enumerate(r[:3]):
+            arrays[f"region{i}_graph{j}_edge_index"] = g.edge_index.numpy()
+            arrays[f"region{i}_graph{j}_edge_attr"] = g.edge_attr.numpy()
+        arrays[f"region{i}_h3_indices"] = np.asarray(list(r[3]), dtype=np.int64)
+    np.savez_compressed(os.path.join(OUT, "dynamic_graph_builder.npz"), **arrays)
+    print("dynamic_graph_builder", {k: v.shape for k, v in arrays.items()})
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ns = load_reference()
@@ -180,6 +239,7 @@ def main():
     assimilator_case(ns)
     graphcast_case(ns)
     regional_case(ns)
+    live_reference_cases(ns)
 
 
 if __name__ == "__main__":

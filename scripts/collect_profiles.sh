@@ -4,7 +4,7 @@ TAG=${1:-r06}; R=${2:-r06}; S=gpurun_out/$TAG; D=profiles
 cp $S/env.log $D/${R}_env.log
 cp $S/pytest_gpu.log $D/${R}_pytest_gpu.log
 cp $S/smoke.log $D/${R}_smoke.log
-cp $S/bench___steps_20___warmup_5_.log $D/${R}_bench_default.log
+cp $S/bench___full___steps_20___warmup_5_.log $D/${R}_bench_default.log
 for c in c2 c2x3 c3; do cp $S/${c}_kernel_stats.csv $D/${R}_${c}_kernel_stats.csv; done
 for p in fp32 bf16x3; do [ -f $S/train_${p}_kernel_stats.csv ] && cp $S/train_${p}_kernel_stats.csv $D/${R}_train_${p}_kernel_stats.csv; done
 for c in c2 c2x3; do

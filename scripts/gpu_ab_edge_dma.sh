@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 python -c "import __graft_entry__ as g; g.build()" > $OUT/build.log 2>&1 || { echo BUILD FAILED; tail -20 $OUT/build.log; exit 1; }
 for REP in 1 2; do for V in 0 1; do
   rm -rf /tmp/prof && mkdir -p /tmp/prof
-  (cd /tmp && GW_EDGE_DMA6=$V timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o gw -- python $R/bench.py --config c2 --steps 10 --warmup 3 --no-cpu-baseline --no-extra > $R/$OUT/rocprof_$V.log 2>&1)
+  (cd /tmp && GW_EDGE_DMA6=$V timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o gw -- python $R/bench.py --full --config c2 --steps 10 --warmup 3 --no-cpu-baseline --no-extra > $R/$OUT/rocprof_$V.log 2>&1)
   find /tmp/prof -name "*kernel_stats*.csv" -exec cp {} $OUT/k_$V.csv \; 2>/dev/null
   echo "== GW_EDGE_DMA6=$V (rep $REP): $(grep -o '"value": [0-9.]*' $OUT/rocprof_$V.log | tail -n 1)"
   python - $OUT/k_$V.csv <<'PY'

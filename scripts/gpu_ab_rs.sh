@@ -10,7 +10,7 @@ for CFG in c2 c2x3; do
   for V in "GW_NODE_RS=0" "GW_NODE_RS=1 GW_RS_TUNE=1" "GW_NODE_RS=1 GW_RS_TUNE=0"; do
     N=$(echo "$V" | tr -c 'a-zA-Z0-9' '_')
     rm -rf /tmp/prof && mkdir -p /tmp/prof
-    (cd /tmp && env $V timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o gw -- python $R/bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --no-extra > $R/$OUT/rocprof_${CFG}_$N.log 2>&1)
+    (cd /tmp && env $V timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o gw -- python $R/bench.py --full --config $CFG --steps 10 --warmup 3 --no-cpu-baseline --no-extra > $R/$OUT/rocprof_${CFG}_$N.log 2>&1)
     find /tmp/prof -name "*kernel_stats*.csv" -exec cp {} $OUT/${CFG}_${N}_kernel_stats.csv \; 2>/dev/null
     echo "== $CFG $V: $(grep -o '"value": [0-9.]*' $OUT/rocprof_${CFG}_$N.log | tail -n 1) forecasts/s under rocprofv3"
     python - $OUT/${CFG}_${N}_kernel_stats.csv <<'PY'

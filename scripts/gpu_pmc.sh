@@ -4,12 +4,13 @@ TAG=${1:-pmc}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
+R=$(pwd)
 cd /tmp
 rocprofv3 -L > $GRAFT_REPO_ROOT/$OUT/counters_list.txt 2>&1
 run_pass () {
   name=$1; shift
   rm -rf /tmp/pmc_$name
-  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d /tmp/pmc_$name -o p -- python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extra > $GRAFT_REPO_ROOT/$OUT/run_$name.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d /tmp/pmc_$name -o p -- python $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extra > $R/$OUT/run_$name.log 2>&1
   echo "rc=$?" >> $GRAFT_REPO_ROOT/$OUT/run_$name.log
   f=$(find /tmp/pmc_$name -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then

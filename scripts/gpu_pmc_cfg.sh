@@ -4,7 +4,7 @@
 #                                                           + gpurun_out/TAG/pmc_CONFIG_dominant.json: the edge-update instantiation with the
 #                                                             largest grid (the decoder edge update) in the flat form bench.pmc_traffic() reads
 #                                                             (copied to profiles/rNN_pmc_CONFIG.json by scripts/gpu_final.sh)
-# PMC_CMD (optional): the bench.py arguments of the profiled run instead of "--config CONFIG --steps 3 --warmup 1 --no-cpu-baseline
+# PMC_CMD (optional): the bench.py arguments of the profiled run instead of "--full --config CONFIG --steps 3 --warmup 1 --no-cpu-baseline
 # --no-extra" - e.g. the training step: PMC_CMD="--mode train --precision bf16x3 --steps 2 --warmup 1" scripts/gpu_pmc_cfg.sh TAG train_x3
 # "(bwd_chainx3_kernel|gemm_tn_x3_kernel)<[^>]*>"
 # HBM bytes: FETCH_SIZE x 2 (gfx950 correction, MI355X_MICROARCH.md) and WRITE_SIZE, both in KiB; MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES /
@@ -13,7 +13,7 @@ TAG=${1:-pmc}; CFG=${2:-c2}; RX=${3:-"(chainx3_kernel|chain_kernel|edge_kernel|c
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-CMD=${PMC_CMD:-"--config $CFG --steps 3 --warmup 1 --no-cpu-baseline --no-extra"}
+CMD=${PMC_CMD:-"--full --config $CFG --steps 3 --warmup 1 --no-cpu-baseline --no-extra"}
 cd /tmp
 run_pass () {
   name=$1; shift

@@ -10,7 +10,7 @@ cd /tmp
 run_pass () {
   name=$1; shift
   rm -rf /tmp/pmcic_$name
-  timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d /tmp/pmcic_$name -o p -- python $R/bench.py --config $CFG --steps 3 --warmup 1 --no-cpu-baseline --no-extra > $R/$OUT/run_ic_${CFG}_$name.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d /tmp/pmcic_$name -o p -- python $R/bench.py --full --config $CFG --steps 3 --warmup 1 --no-cpu-baseline --no-extra > $R/$OUT/run_ic_${CFG}_$name.log 2>&1
   echo "rc=$?" >> $R/$OUT/run_ic_${CFG}_$name.log
   f=$(find /tmp/pmcic_$name -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && cp "$f" /tmp/rawic_${CFG}_$name.csv

@@ -6,7 +6,7 @@
 #   test[:EXPR]            pytest -m gpu (EXPR = -k expression or a test file path)
 #   smoke                  __graft_entry__.smoke()
 #   bench[:ARGS]           python bench.py ARGS (default: the driver's command, --steps 20 --warmup 5); ARGS with '+' for spaces
-#   prof:CONFIG            rocprofv3 --kernel-trace --stats of bench.py --config CONFIG --steps 5 (kernel_stats csv copied)
+#   prof:CONFIG            rocprofv3 --kernel-trace --stats of bench.py --full --config CONFIG --steps 5 (kernel_stats csv copied)
 #   proftrain[:PRECISION]  rocprofv3 --kernel-trace --stats of the training step (bench.py --mode train --steps 3; fp32 or bf16x3)
 #   pmc:c3 | pmc:c2        the multi-pass PMC scripts (scripts/gpu_pmc_c3.sh, scripts/gpu_pmc.sh): summary json under gpurun_out/TAG
 #   py:SCRIPT[:ARGS]       python SCRIPT ARGS (probes under scripts/probes)
@@ -33,7 +33,7 @@ for STEP in "$@"; do
       timeout 1200 python bench.py ${A//+/ } > $OUT/bench_$N.log 2>&1; echo "bench rc=$?" >> $OUT/bench_$N.log; tail -n 2 $OUT/bench_$N.log | cut -c1-3500 ;;
     prof)
       rm -rf /tmp/prof && mkdir -p /tmp/prof
-      (cd /tmp && GW_AUTO_GRAPH=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o gw -- python $R/bench.py --config $ARG --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $R/$OUT/rocprof_$ARG.log 2>&1)  # (eager launches: the same kernels the HIP graph replays)
+      (cd /tmp && GW_AUTO_GRAPH=0 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o gw -- python $R/bench.py --full --config $ARG --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $R/$OUT/rocprof_$ARG.log 2>&1)  # (eager launches: the same kernels the HIP graph replays)
       find /tmp/prof -name "*kernel_stats*.csv" -exec cp {} $OUT/${ARG}_kernel_stats.csv \; 2>/dev/null
       tail -n 1 $OUT/rocprof_$ARG.log | cut -c1-600; head -n 16 $OUT/${ARG}_kernel_stats.csv | cut -c1-200 ;;
     proftrain)

@@ -2,9 +2,9 @@
 exchange with the reference's own classes.
 
 CPU: the alias exposes the hot-path names of ``graph_weather/__init__.py:8-9`` and ``graph_weather/models/__init__.py:13-15``;
-the ``state_dict()`` of the reference's OWN ``GraphWeatherForecaster`` / ``GraphCast`` (executed from /root/reference through
-``oracle/refload.py``, build container only) loads with ``strict=True`` and has exactly the key -> shape table the GPU test
-below rebuilds without the reference.
+the ``state_dict()`` layout of the reference's OWN ``GraphWeatherForecaster`` / ``GraphCast`` (key -> shape tables recorded
+from the reference's classes by ``oracle/gen_golden.py``) loads with ``strict=True`` and is exactly the key -> shape table the
+GPU test below rebuilds without the reference.
 GPU: a state_dict keyed and shaped like the reference's (built from that table, not from our module) loads ``strict=True``
 into the alias' model and reproduces the golden output of the reference's own class.
 """
@@ -17,7 +17,6 @@ import pytest
 import torch
 
 from graph_weather_amd.utils import deterministic_fill_, regular_lat_lons, seeded_features
-from oracle.refload import reference_available
 
 from .helpers import forecaster_param_shapes, make_params
 
@@ -68,18 +67,19 @@ def test_alias_exposes_the_reference_import_paths():
     assert GraphWeatherForecasterConfig is gw.GraphWeatherForecasterConfig and callable(validate_lat_lons)
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not reference_available(), reason="/root/reference not present (GPU box)")
-def test_reference_state_dicts_load_strict():
-    """state_dict() of the reference's own classes -> load_state_dict(strict=True) of ours, and back."""
-    import graph_weather_amd as gw
-    from oracle.refload import load_reference
+def test_reference_state_dicts_load_strict(golden_dir):
+    """state_dict() of the reference's own classes -> load_state_dict(strict=True) of ours, and back: the key -> shape tables
+    of the reference's GraphWeatherForecaster / GraphCast (recorded in tests/golden/reference_state_dict_shapes.json by
+    oracle/gen_golden.py) filled with the per-key seeded values."""
+    import json
 
-    ns = load_reference()
+    import graph_weather_amd as gw
+
+    with open(os.path.join(golden_dir, "reference_state_dict_shapes.json")) as fh:
+        tables = json.load(fh)
     lat_lons = regular_lat_lons(30.0)
-    ref = ns.GraphWeatherForecaster(lat_lons)
-    deterministic_fill_(ref, seed=5)
-    sd = ref.state_dict()
+    ref_table = {k: tuple(v) for k, v in tables["GraphWeatherForecaster(regular_lat_lons(30.0))"].items()}
+    sd = make_params(ref_table, seed=5)
     ours = gw.GraphWeatherForecaster(lat_lons)
     res = ours.load_state_dict(sd, strict=True)
     assert not res.missing_keys and not res.unexpected_keys
@@ -87,14 +87,15 @@ def test_reference_state_dicts_load_strict():
         assert torch.equal(v, sd[k]), k
     # the key -> shape table the GPU test rebuilds without the reference is exactly the reference's
     table = forecaster_param_shapes(ours.encoder.num_h3)
-    assert {k: tuple(v.shape) for k, v in sd.items()} == table
-    ref.load_state_dict(ours.state_dict(), strict=True)  # and the other way round
+    assert ref_table == table
+    # and the other way round: ours has exactly the reference's keys and shapes, so the reference loads it strict=True
+    assert {k: tuple(v.shape) for k, v in ours.state_dict().items()} == ref_table
     # GraphCast wrapper (graphcast/model.py): same sub-module names
-    refc = ns.GraphCast(lat_lons)
+    refc_table = {k: tuple(v) for k, v in tables["GraphCast(regular_lat_lons(30.0))"].items()}
     oursc = gw.GraphCast(lat_lons)
-    res = oursc.load_state_dict(refc.state_dict(), strict=True)
+    res = oursc.load_state_dict(make_params(refc_table, seed=5), strict=True)
     assert not res.missing_keys and not res.unexpected_keys
-    refc.load_state_dict(oursc.state_dict(), strict=True)
+    assert {k: tuple(v.shape) for k, v in oursc.state_dict().items()} == refc_table
 
 
 def test_topology_hash_and_check():

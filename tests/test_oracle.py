@@ -1,6 +1,6 @@
 """The CPU oracle against (a) golden vectors produced by the reference's own source files,
-(b) the reference executed live when /root/reference exists, (c) the invariants the reference's
-tests state."""
+(b) the graphs, weights and output of a small run of the reference's own forecaster (recorded in
+tests/golden), (c) the invariants the reference's tests state."""
 import os
 
 import numpy as np
@@ -10,7 +10,6 @@ import torch
 from graph_weather_amd.graphs import build_forecast_graphs
 from graph_weather_amd.utils import deterministic_fill_, regular_lat_lons, seeded_features
 from oracle import reference_math as om
-from oracle.refload import reference_available
 
 from .helpers import forecaster_param_shapes, make_params
 
@@ -109,28 +108,32 @@ def test_loss_closed_form():
     assert abs(loss.item() - w.mean()) < 1e-4
 
 
-@pytest.mark.reference
-@pytest.mark.skipif(not reference_available(), reason="/root/reference not present (GPU box)")
-def test_oracle_matches_live_reference_small():
-    from oracle.refload import load_reference
+def test_oracle_matches_live_reference_small(golden_dir):
+    """The reference's own GraphWeatherForecaster on the 30 degree grid, B=3 (its graphs, weight digests and output recorded in
+    tests/golden/forecaster_30deg_b3.npz by oracle/gen_golden.py): same graphs, same weights, same output from the oracle."""
+    import hashlib
 
-    ns = load_reference()
+    import graph_weather_amd as gw
+
+    g = _load(golden_dir, "forecaster_30deg_b3.npz")
     lat_lons = regular_lat_lons(30.0)
-    model = ns.GraphWeatherForecaster(lat_lons)
-    deterministic_fill_(model, seed=5)
-    model.eval()
     feats = seeded_features(3, len(lat_lons), seed=9)
-    with torch.no_grad():
-        y_ref = model(feats)
     graphs = build_forecast_graphs(lat_lons, 2)
-    assert torch.equal(model.encoder.graph.edge_index, graphs.enc_edge_index)
-    assert torch.equal(model.encoder.latent_graph.edge_index, graphs.lat_edge_index)
-    assert torch.equal(model.decoder.graph.edge_index, graphs.dec_edge_index)
-    assert torch.allclose(model.decoder.graph.edge_attr, graphs.dec_edge_attr, atol=1e-7)
+    assert torch.equal(torch.from_numpy(g["enc_edge_index"]), graphs.enc_edge_index)
+    assert torch.equal(torch.from_numpy(g["lat_edge_index"]), graphs.lat_edge_index)
+    assert torch.equal(torch.from_numpy(g["dec_edge_index"]), graphs.dec_edge_index)
+    assert torch.allclose(torch.from_numpy(g["dec_edge_attr"]), graphs.dec_edge_attr, atol=1e-7)
+    # the seeded weights depend on (key, shape, seed) only: filled into a module with the reference's keys they are the
+    # reference's weights, byte for byte
+    model = gw.GraphWeatherForecaster(lat_lons)
+    deterministic_fill_(model, seed=5)
     p = {k: v.clone() for k, v in model.state_dict().items()}
-    assert set(p.keys()) == set(forecaster_param_shapes(graphs.num_mesh).keys())
+    keys = g["state_keys"].tolist()
+    assert set(p.keys()) == set(keys) == set(forecaster_param_shapes(graphs.num_mesh).keys())
+    for k, digest in zip(keys, g["state_sha256"].tolist()):
+        assert hashlib.sha256(p[k].contiguous().numpy().tobytes()).hexdigest() == digest, k
     y = om.forecaster_forward(p, graphs.as_oracle_dict(), feats)
-    assert torch.allclose(y, y_ref, rtol=1e-5, atol=1e-5)
+    assert torch.allclose(y, torch.from_numpy(g["y"]), rtol=1e-5, atol=1e-5)
 
 
 def _assimilator_setup():

@@ -343,6 +343,49 @@ def test_bench_self_launch_from_a_clean_environment(tmp_path):
     assert r.returncode != 0
 
 
+def test_bench_plain_run_dumps_the_last_step_and_measures_nothing_else(tmp_path):
+    """A plain bench line (no --full) carries the headline fields and no extra measurement; --dump-outputs writes the last timed
+    step's forecast as float32, identical from run to run (seeded inputs); the sample of an output above the budget is fixed."""
+    import contextlib
+    import io
+    import json
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+
+    import gc
+
+    lines = []
+    try:
+        for run in ("a", "b"):
+            buf = io.StringIO()
+            with contextlib.redirect_stdout(buf):
+                bench.main(["--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / run)], device="cpu",
+                           model_factory=_stub_factory)
+            lines.append(buf.getvalue().strip().splitlines())
+    finally:
+        gc.unfreeze()  # bench.main freezes the heap before its timed region; this process goes on with other tests
+    assert all(len(out) == 1 for out in lines)
+    d = json.loads(lines[0][0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "forecasts/s" and d["higher_is_better"] is True
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 2 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "extra" not in d and "cold_ms_per_step" not in d
+    a, b = np.load(tmp_path / "a" / "forecast.npy"), np.load(tmp_path / "b" / "forecast.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 72, 78) and np.array_equal(a, b)
+    big = torch.arange(40 * 1000 * 8, dtype=torch.float32).reshape(40, 1000, 8)
+    for run in ("c", "d"):
+        bench.dump_outputs(str(tmp_path / run), {"forecast": big, "loss": torch.ones(1, dtype=torch.float64)}, budget=64 * 1024)
+    c, lc = np.load(tmp_path / "c" / "forecast.npy"), np.load(tmp_path / "c" / "loss.npy")
+    assert lc.dtype == np.float64 and c.dtype == np.float32 and c.shape[1] == 8 and c.nbytes + lc.nbytes <= 64 * 1024
+    assert np.array_equal(c, np.load(tmp_path / "d" / "forecast.npy"))
+    rows = c[:, 0] / 8
+    assert np.all(np.diff(rows) > 0) and np.array_equal(c, big.reshape(-1, 8).numpy()[rows.astype(np.int64)])
+
+
 _FAIL_CALLS = {"n": 0}
 
 
