@@ -823,9 +823,13 @@ int gw_gemm_f32(int32_t mode, int64_t m, int32_t n, int64_t k, const float* a, i
     return fail(GW_E_BADARG, "gw_gemm_f32: bad arguments");
   const bool x3 = mode == GW_GEMM_TN_BF16X3;
   if (x3) mode = GW_GEMM_TN;
-  if (m == 0 || n == 0) return GW_OK;
+  if (m == 0) return GW_OK;
   if (m >= ((int64_t)1 << 31) || k >= ((int64_t)1 << 31)) return fail(GW_E_UNSUPPORTED, "gw_gemm_f32: dimension exceeds int32");
   if (colsum_a && mode != GW_GEMM_TN) return fail(GW_E_UNSUPPORTED, "gw_gemm_f32: colsum_a is a TN-mode extra");
+  if (n == 0) {  // no product, but the column sums of A are still owed (colsum_a[m] += sum_k A[k][m]): the plain column-sum path
+    if (!colsum_a || k == 0) return GW_OK;
+    return gw_relu_backward(k, (int32_t)m, a, lda, nullptr, 0, nullptr, 0, colsum_a, stream);
+  }
   const dim3 block(256);
   if (mode == GW_GEMM_TN) {
     if (k == 0) return GW_OK;  // nothing to add
@@ -948,7 +952,8 @@ int gw_normalized_mse_backward(const float* pred, const float* target, const flo
   if (!pred || !target || !lat_weights || !dloss || !dpred || num_unique_lat <= 0 || batch <= 0 || nodes <= 0 || channels <= 0)
     return fail(GW_E_BADARG, "gw_normalized_mse_backward: bad arguments");
   const int num_lon = nodes / num_unique_lat;
-  if (num_lon <= 0) return fail(GW_E_BADARG, "gw_normalized_mse_backward: nodes must equal num_unique_lat * num_lon");
+  if (num_lon <= 0 || (nodes + num_lon - 1) / num_lon > num_unique_lat)  // the forward's check: lat_weights[n / num_lon] in range
+    return fail(GW_E_BADARG, "gw_normalized_mse_backward: nodes must equal num_unique_lat * num_lon");
   const size_t total = (size_t)batch * nodes * channels;
   const float scale = 1.0f / ((float)channels * (float)batch * (float)nodes);
   int grid = (int)((total + 1023) / 1024);

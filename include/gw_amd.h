@@ -377,7 +377,7 @@ typedef struct gw_activation_save {
                                shape, leading dimension and alignment (v19; before: multiples of 128 only, other shapes on
                                the fp32 kernel) */
 int gw_gemm_f32(int32_t mode, int64_t m, int32_t n, int64_t k, const float* a, int32_t lda, const float* b, int32_t ldb,
-                float* c, int32_t ldc, float* colsum_a /* TN only, may be NULL: colsum_a[m] += sum_k A[k][m] (bias gradient) */,
+                float* c, int32_t ldc, float* colsum_a /* TN only, may be NULL: colsum_a[m] += sum_k A[k][m] (bias gradient; n == 0 too) */,
                 void* stream);
 /* nn.ReLU backward fused with the nn.Linear bias gradient: dz = dh * (h > 0) (h NULL: dz = dh), db[c] += sum_r dz[r][c].
  * dz may alias dh or be NULL (bias gradient only); db may be NULL.  Any width (above 256: wide models, csrc/gw_wide.hip). */
@@ -397,7 +397,7 @@ int gw_gather_rows(int32_t batch, int32_t n_idx, const float* table, int32_t row
  * batch_out == batch: per sample; batch_out == 1: summed over the batch too (gradient of a batch-shared table). */
 int gw_segment_sum_rows(int32_t batch, int32_t batch_out, int32_t n_seg, const float* rows, int32_t rows_per_batch_in,
                         const int32_t* perm, const int32_t* ptr, float* out, int32_t accumulate, void* stream);
-/* NormalizedMSELoss backward (losses.py:66-94): dpred = dloss * d loss / d pred. */
+/* NormalizedMSELoss backward (losses.py:66-94): dpred = dloss * d loss / d pred; refuses the shapes the forward refuses. */
 int gw_normalized_mse_backward(const float* pred, const float* target, const float* inv_var, int32_t inv_var_full,
                                const float* lat_weights,
                                int32_t num_unique_lat, int32_t batch, int32_t nodes, int32_t channels, const float* dloss,

@@ -461,3 +461,32 @@ def test_processor_form_on_segment_tiles_stays_inside_its_buffers(half, B, n, de
         return out
 
     _both(run)
+
+
+@pytest.mark.parametrize("nodes,num_unique_lat", [(10, 3), (11, 5), (15, 4)])
+def test_normalized_mse_backward_refuses_what_the_forward_refuses(nodes, num_unique_lat):
+    """nodes / num_unique_lat rounds down to num_lon, and the loss reads lat_weights[node / num_lon]: a shape whose last node
+    falls past the weight table is refused by the forward, and must be refused by the backward with the same check (it
+    launched, and read past the table, before) - with nothing launched and nothing written."""
+    from graph_weather_amd import _lib
+
+    L = _lib.lib()
+    st = torch.cuda.current_stream().cuda_stream
+    pred = torch.zeros(nodes, 4, device=DEV)
+    target = torch.zeros(nodes, 4, device=DEV)
+    w = torch.ones(num_unique_lat, device=DEV)
+    dl = torch.ones(1, device=DEV)
+    dp = torch.full((nodes, 4), 5.0, device=DEV)
+    loss = torch.zeros(1, device=DEV)
+    rc_f = L.gw_normalized_mse_forward(pred.data_ptr(), target.data_ptr(), None, 0, w.data_ptr(), num_unique_lat, 1, nodes, 4,
+                                       loss.data_ptr(), st)
+    rc_b = L.gw_normalized_mse_backward(pred.data_ptr(), target.data_ptr(), None, 0, w.data_ptr(), num_unique_lat, 1, nodes, 4,
+                                        dl.data_ptr(), dp.data_ptr(), st)
+    torch.cuda.synchronize()
+    assert rc_f == -1 and rc_b == -1, (rc_f, rc_b)  # GW_E_BADARG, both
+    assert torch.all(dp == 5.0)
+    # the shapes next to them that fit the table are accepted by both
+    ok_nodes = num_unique_lat * (nodes // num_unique_lat)
+    _lib.check(L.gw_normalized_mse_backward(pred.data_ptr(), target.data_ptr(), None, 0, w.data_ptr(), num_unique_lat, 1, ok_nodes, 4,
+                                            dl.data_ptr(), dp.data_ptr(), st), "nmse backward")
+    torch.cuda.synchronize()
