@@ -28,6 +28,7 @@ EXPORTS = [
     "gw_normalized_mse_forward", "gw_gemm_f32", "gw_relu_backward", "gw_layernorm_backward", "gw_gather_rows",
     "gw_segment_sum_rows", "gw_normalized_mse_backward", "gw_adamw_step", "gw_nudging_forward", "gw_nudging_backward",
     "gw_linear_forward", "gw_linear_gather_forward", "gw_layernorm_forward", "gw_add_rows", "gw_gather_rows_wide", "gw_segment_sum_rows_wide",
+    "gw_constraint_workspace_bytes", "gw_constraint_forward", "gw_constraint_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -51,6 +52,16 @@ PACK_MAX_ITEMS = 16
 class GwPackItem(Structure):  # include/gw_amd.h: gw_pack_item
     _fields_ = [("w", c_void_p), ("stride_f", c_int64), ("stride_k", c_int64), ("n_out", c_int32), ("kseg", c_int32),
                 ("rows", c_int32), ("reserved", c_int32), ("out", c_void_p)]
+
+
+CONSTRAINT_TYPES = {"additive": 1, "multiplicative": 2, "softmax": 3}  # GW_CONSTRAINT_*
+
+
+class GwConstraintArgs(Structure):  # include/gw_amd.h: gw_constraint_args
+    _fields_ = [("type", c_int32), ("batch", c_int32), ("nodes", c_int32), ("channels", c_int32), ("cells", c_int32),
+                ("f", c_int32), ("grid_h", c_int32), ("grid_w", c_int32), ("graph_rows", c_int32), ("exp_factor", c_float),
+                ("hr", c_void_p), ("ld_hr", c_int32), ("lr", c_void_p), ("ld_lr", c_int32), ("map", c_void_p),
+                ("inv_ptr", c_void_p), ("inv_idx", c_void_p)]
 
 
 class GwPadItem(Structure):  # include/gw_amd.h: gw_pad_item
@@ -206,6 +217,13 @@ def lib():
     L.gw_segment_sum_rows_wide.restype = c_int
     L.gw_segment_sum_rows_wide.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                            c_int32, c_void_p]
+    L.gw_constraint_workspace_bytes.restype = c_size_t
+    L.gw_constraint_workspace_bytes.argtypes = [POINTER(GwConstraintArgs)]
+    L.gw_constraint_forward.restype = c_int
+    L.gw_constraint_forward.argtypes = [POINTER(GwConstraintArgs), c_void_p, c_size_t, c_void_p, c_int32, c_void_p]
+    L.gw_constraint_backward.restype = c_int
+    L.gw_constraint_backward.argtypes = [POINTER(GwConstraintArgs), c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_int32, c_void_p,
+                                         c_int32, c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

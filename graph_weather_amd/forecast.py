@@ -11,6 +11,7 @@ from typing import Optional
 
 import torch
 
+from .constraint import TYPES as CONSTRAINT_TYPES, PhysicalConstraintLayer
 from .graphed import AutoGraphModule
 from .graphs import TopologyRecord, build_forecast_graphs
 from .layers import Decoder, Encoder, Processor, fused_forward, set_compute_dtype
@@ -50,7 +51,8 @@ class GraphWeatherForecasterConfig:
 
 
 class GraphWeatherForecaster(AutoGraphModule, TopologyRecord, torch.nn.Module, PyTorchModelHubMixin):
-    """forecast.py:61-247 (constraint layer and thermalizer are optional extras outside the hot path)."""
+    """forecast.py:61-247 (the thermalizer is an optional extra outside the hot path; the constraint layer runs on
+    csrc/gw_constraint.hip)."""
 
     def __init__(self, lat_lons: list, resolution: int = 2, feature_dim: int = 78, aux_dim: int = 24,
                  output_dim: Optional[int] = None, node_dim: int = 256, edge_dim: int = 256, num_blocks: int = 9,
@@ -59,8 +61,10 @@ class GraphWeatherForecaster(AutoGraphModule, TopologyRecord, torch.nn.Module, P
                  hidden_dim_decoder: int = 128, hidden_layers_decoder: int = 2, norm_type: str = "LayerNorm",
                  use_checkpointing: bool = False, constraint_type: str = "none", use_thermalizer: bool = False):
         super().__init__()
-        if constraint_type != "none":
-            raise NotImplementedError("PhysicalConstraintLayer (default 'none', forecast.py:82) is outside the hot path")
+        if constraint_type not in ("none",) + CONSTRAINT_TYPES:
+            # the reference accepts any string here and raises ValueError("Unknown constraint type") in its first forward
+            raise ValueError("Unknown constraint type: %r (one of 'none', %s)"
+                             % (constraint_type, ", ".join(repr(t) for t in CONSTRAINT_TYPES)))
         self.feature_dim = feature_dim
         self.constraint_type = constraint_type
         self.use_thermalizer = use_thermalizer
@@ -78,6 +82,11 @@ class GraphWeatherForecaster(AutoGraphModule, TopologyRecord, torch.nn.Module, P
         self.grid_shape = (len(unique_lats), len(unique_lons))
         self.original_lat_lons = list(lat_lons)
         self._create_grid_mapping(unique_lats, unique_lons)
+        if constraint_type != "none" and self.grid_shape[0] * self.grid_shape[1] != len(lat_lons):
+            # forecast.py:235 rearranges the decoder output "b (h w) c -> b c h w": it fails there in the first forward
+            raise ValueError("graph_weather_amd: constraint_type %r needs one node per cell of the %d x %d lat / lon grid, got %d "
+                             "nodes (forecast.py:235 reshapes the output to that grid)"
+                             % (constraint_type, self.grid_shape[0], self.grid_shape[1], len(lat_lons)))
         graphs = build_forecast_graphs(lat_lons, resolution)  # built once, shared by encoder and decoder
         self.encoder = Encoder(lat_lons=lat_lons, resolution=resolution, input_dim=feature_dim + aux_dim,
                                output_dim=node_dim, output_edge_dim=edge_dim,
@@ -99,6 +108,9 @@ class GraphWeatherForecaster(AutoGraphModule, TopologyRecord, torch.nn.Module, P
                                hidden_layers_processor_edge=hidden_layers_processor_edge, mlp_norm_type=norm_type,
                                hidden_dim_decoder=hidden_dim_decoder, hidden_layers_decoder=hidden_layers_decoder,
                                use_checkpointing=use_checkpointing, _graphs=graphs)
+        if constraint_type != "none":  # forecast.py:170-176 (holds the model without registering it: no module cycle)
+            self.constraint = PhysicalConstraintLayer(model=self, grid_shape=self.grid_shape, constraint_type=constraint_type,
+                                                      upsampling_factor=1)
 
     def set_compute_dtype(self, dtype) -> "GraphWeatherForecaster":
         """float32 (default), bfloat16 or "bf16x3" (split-operand) matrix products - see ``layers.set_compute_dtype``."""
@@ -148,7 +160,7 @@ class GraphWeatherForecaster(AutoGraphModule, TopologyRecord, torch.nn.Module, P
         return graph
 
     def forward(self, features: torch.Tensor, t: int = 0) -> torch.Tensor:
-        """forecast.py:215-247 with constraint_type == "none".  Fused path: data stays in the native layouts
+        """forecast.py:215-247.  Fused path: data stays in the native layouts
         (dst-sorted shared graph, cached batch-independent embeddings) between encoder, processor and decoder.  In eval() under
         no_grad() the call replays its own HIP graph from the third call of a shape on (graphed.AutoGraphModule)."""
         y = self._auto_graph_step(features)
@@ -163,4 +175,9 @@ class GraphWeatherForecaster(AutoGraphModule, TopologyRecord, torch.nn.Module, P
             raise RuntimeError("graph_weather_amd: features must be [B, nodes, >= %d channels]" % self.output_dim)
         features = features.contiguous()
         B, G = int(features.shape[0]), self.encoder.num_latlons
-        return fused_forward(self.encoder, self.processor, self.decoder, features, features.reshape(B * G, features.shape[2]))
+        y = fused_forward(self.encoder, self.processor, self.decoder, features, features.reshape(B * G, features.shape[2]))
+        if self.constraint_type != "none":
+            # forecast.py:234-246: the output read as [B, H*W] grid rows, the input's first feature_dim channels as the
+            # low-resolution reference (read in place through the features' row stride)
+            y = self.constraint.apply_rows(y.reshape(B, G, self.output_dim), features)
+        return y

@@ -450,6 +450,52 @@ int gw_gather_rows_wide(int32_t batch, int32_t n_idx, int32_t width, const float
 int gw_segment_sum_rows_wide(int32_t batch, int32_t batch_out, int32_t n_seg, int32_t width, const float* rows, int32_t ld,
                              int32_t rows_per_batch_in, const int32_t* perm, const int32_t* ptr, float* out, int32_t ldo, void* stream);
 
+/* =====================================================================================================================
+ * PhysicalConstraintLayer (graph_weather/models/layers/constraint_layer.py) behind the decoder (forecast.py:234-246),
+ * csrc/gw_constraint.hip.  The reference's grid round trip (graph_to_grid / grid_to_graph, last writer wins) reduces to a
+ * gather through a node -> row map: node n reads row map[n] of hr (the decoder output as grid rows) and of lr (the input's
+ * first channels).  With h = hr[b, map[n], c], l = lr[b, map[n], c] and means over all `nodes` nodes:
+ *   GW_CONSTRAINT_ADDITIVE        out[b, n, c] = h + (l - mean_m hr[b, map[m], c])
+ *   GW_CONSTRAINT_MULTIPLICATIVE  out[b, n, c] = h * (mean_m lr[b, map[m], c] / (mean_m hr[b, map[m], c] + 1e-8))
+ *   GW_CONSTRAINT_SOFTMAX, f = 1  out[b, n, c] = e * (l * (1 / e)), e = exp(exp_factor * h)   (the reference's order of
+ *                                 operations: inf / NaN exactly where it overflows)
+ *   GW_CONSTRAINT_SOFTMAX, f > 1  E = exp(exp_factor * hr) on the grid_h x grid_w grid of rows, S = (f x f block mean of E) * f^2,
+ *                                 out[b, n, c] = E[map[n]] * (lr[b, block(map[n]), c] * (1 / S[block(map[n])])); lr then holds
+ *                                 (grid_h / f) * (grid_w / f) rows per sample
+ * hr = [batch, cells, channels] rows ld_hr floats apart, lr the same with ld_lr (lr may be the forecaster's input rows: ld_lr =
+ * feature_dim + aux_dim); inv_ptr[cells + 1] / inv_idx[nodes] = CSR of map's inverse (row k -> the nodes reading it, ascending).
+ * map values must lie in [0, cells): they are not checked on the device.  The statistics are reduced in one fixed order
+ * (fp64 partials per slab of rows, no atomics): results are bitwise reproducible.  More than 2^31-1 elements in any
+ * operand: GW_E_UNSUPPORTED. */
+#define GW_CONSTRAINT_ADDITIVE 1
+#define GW_CONSTRAINT_MULTIPLICATIVE 2
+#define GW_CONSTRAINT_SOFTMAX 3
+typedef struct gw_constraint_args {
+  int32_t type;        /* GW_CONSTRAINT_* */
+  int32_t batch, nodes, channels, cells;
+  int32_t f;           /* softmax block size (upsampling_factor); 1 for the other types */
+  int32_t grid_h, grid_w; /* f > 1: grid_h * grid_w == cells, both multiples of f */
+  int32_t graph_rows;  /* 1: hr rows are graph nodes (3-D layer input): rows no node reads get a zero gradient */
+  float exp_factor;
+  const float* hr;
+  int32_t ld_hr;
+  const float* lr;
+  int32_t ld_lr;
+  const int32_t* map;
+  const int32_t* inv_ptr;
+  const int32_t* inv_idx;
+} gw_constraint_args;
+/* Workspace both calls need (0 for the softmax with f = 1; 0 with the error set on bad arguments). */
+size_t gw_constraint_workspace_bytes(const gw_constraint_args* a);
+/* out[b, n, :channels] (row stride ld_out); out must not alias hr or lr. */
+int gw_constraint_forward(const gw_constraint_args* a, void* workspace, size_t workspace_bytes, float* out, int32_t ld_out,
+                          void* stream);
+/* Gradients for dout [batch, nodes, channels] (ld_dout): dhr [batch, cells, :channels] is written in full (rows no node reads:
+ * zero, except the softmax on a dense 4-D grid, which like the reference computes them from a zero gradient); dlr rows
+ * [batch, lr rows, :channels] are written, other columns of dlr are not touched.  Either output may be NULL. */
+int gw_constraint_backward(const gw_constraint_args* a, const float* dout, int32_t ld_dout, void* workspace, size_t workspace_bytes,
+                           float* dhr, int32_t ld_dhr, float* dlr, int32_t ld_dlr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
