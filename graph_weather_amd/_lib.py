@@ -29,6 +29,10 @@ EXPORTS = [
     "gw_segment_sum_rows", "gw_normalized_mse_backward", "gw_adamw_step", "gw_nudging_forward", "gw_nudging_backward",
     "gw_linear_forward", "gw_linear_gather_forward", "gw_layernorm_forward", "gw_add_rows", "gw_gather_rows_wide", "gw_segment_sum_rows_wide",
     "gw_constraint_workspace_bytes", "gw_constraint_forward", "gw_constraint_backward",
+    "gw_thermal_conv_forward", "gw_thermal_conv_wgrad_workspace_bytes", "gw_thermal_conv_wgrad", "gw_thermal_colsum_workspace_bytes",
+    "gw_thermal_colsum", "gw_thermal_groupnorm_workspace_bytes", "gw_thermal_groupnorm_forward", "gw_thermal_groupnorm_backward",
+    "gw_thermal_maxpool_forward", "gw_thermal_maxpool_backward", "gw_thermal_resize_forward", "gw_thermal_resize_backward",
+    "gw_thermal_rows",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -62,6 +66,27 @@ class GwConstraintArgs(Structure):  # include/gw_amd.h: gw_constraint_args
                 ("f", c_int32), ("grid_h", c_int32), ("grid_w", c_int32), ("graph_rows", c_int32), ("exp_factor", c_float),
                 ("hr", c_void_p), ("ld_hr", c_int32), ("lr", c_void_p), ("ld_lr", c_int32), ("map", c_void_p),
                 ("inv_ptr", c_void_p), ("inv_idx", c_void_p)]
+
+
+THERMAL_MAX_TAPS = 7  # GW_THERMAL_MAX_TAPS
+THERMAL_A_PLAIN, THERMAL_A_GN_RELU, THERMAL_A_DIFFUSE = 0, 1, 2  # GW_THERMAL_A_*
+THERMAL_E_STORE, THERMAL_E_DIFFUSE = 0, 1  # GW_THERMAL_E_*
+THERMAL_ROWS_FINALIZE, THERMAL_ROWS_SCALE, THERMAL_ROWS_AXPY = 0, 1, 2  # GW_THERMAL_ROWS_*
+
+
+class GwThermalTaps(Structure):  # include/gw_amd.h: gw_thermal_taps
+    _fields_ = [("n", c_int32), ("in_off", c_int32 * THERMAL_MAX_TAPS), ("w_idx", c_int32 * THERMAL_MAX_TAPS)]
+
+
+class GwThermalConvArgs(Structure):  # include/gw_amd.h: gw_thermal_conv_args
+    _fields_ = [("batch", c_int32), ("in_h", c_int32), ("in_w", c_int32), ("out_h", c_int32), ("out_w", c_int32), ("q_h", c_int32),
+                ("q_w", c_int32), ("in_scale_h", c_int32), ("in_scale_w", c_int32), ("out_scale_h", c_int32),
+                ("out_scale_w", c_int32), ("out_off_h", c_int32), ("out_off_w", c_int32), ("ty", GwThermalTaps),
+                ("tx", GwThermalTaps), ("cin", c_int32), ("cout", c_int32), ("a_mode", c_int32), ("e_mode", c_int32),
+                ("a", c_void_p), ("ld_a", c_int32), ("features", c_int32), ("a_scale", c_void_p), ("a_shift", c_void_p),
+                ("w", c_void_p), ("w_stride_y", c_int64), ("w_stride_x", c_int64), ("w_stride_ci", c_int64),
+                ("w_stride_co", c_int64), ("bias", c_void_p), ("out", c_void_p), ("ld_out", c_int32), ("ld_x", c_int32),
+                ("x", c_void_p), ("eps", c_void_p), ("sa", c_float), ("s1", c_float)]
 
 
 class GwPadItem(Structure):  # include/gw_amd.h: gw_pad_item
@@ -224,6 +249,39 @@ def lib():
     L.gw_constraint_backward.restype = c_int
     L.gw_constraint_backward.argtypes = [POINTER(GwConstraintArgs), c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_int32, c_void_p,
                                          c_int32, c_void_p]
+    L.gw_thermal_conv_forward.restype = c_int
+    L.gw_thermal_conv_forward.argtypes = [POINTER(GwThermalConvArgs), c_void_p]
+    L.gw_thermal_conv_wgrad_workspace_bytes.restype = c_size_t
+    L.gw_thermal_conv_wgrad_workspace_bytes.argtypes = [POINTER(GwThermalConvArgs)]
+    L.gw_thermal_conv_wgrad.restype = c_int
+    L.gw_thermal_conv_wgrad.argtypes = [POINTER(GwThermalConvArgs), c_void_p, c_size_t, c_void_p, c_void_p]
+    L.gw_thermal_colsum_workspace_bytes.restype = c_size_t
+    L.gw_thermal_colsum_workspace_bytes.argtypes = [c_int64, c_int32]
+    L.gw_thermal_colsum.restype = c_int
+    L.gw_thermal_colsum.argtypes = [c_int64, c_int32, c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_void_p]
+    L.gw_thermal_groupnorm_workspace_bytes.restype = c_size_t
+    L.gw_thermal_groupnorm_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
+    L.gw_thermal_groupnorm_forward.restype = c_int
+    L.gw_thermal_groupnorm_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_float,
+                                               c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_thermal_groupnorm_backward.restype = c_int
+    L.gw_thermal_groupnorm_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_thermal_maxpool_forward.restype = c_int
+    L.gw_thermal_maxpool_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                             c_int32, c_void_p, c_void_p]
+    L.gw_thermal_maxpool_backward.restype = c_int
+    L.gw_thermal_maxpool_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32,
+                                              c_void_p, c_void_p]
+    L.gw_thermal_resize_forward.restype = c_int
+    L.gw_thermal_resize_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                            c_void_p]
+    L.gw_thermal_resize_backward.restype = c_int
+    L.gw_thermal_resize_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p,
+                                             c_void_p]
+    L.gw_thermal_rows.restype = c_int
+    L.gw_thermal_rows.argtypes = [c_int32, c_int64, c_int32, c_float, c_float, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                  c_void_p, c_int32, c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

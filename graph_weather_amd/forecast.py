@@ -15,6 +15,7 @@ from .constraint import TYPES as CONSTRAINT_TYPES, PhysicalConstraintLayer
 from .graphed import AutoGraphModule
 from .graphs import TopologyRecord, build_forecast_graphs
 from .layers import Decoder, Encoder, Processor, fused_forward, set_compute_dtype
+from .thermalizer import timestep
 
 try:  # forecast.py:8,61 - hub mixin gives save_pretrained / from_pretrained / push_to_hub
     from huggingface_hub import PyTorchModelHubMixin
@@ -51,7 +52,7 @@ class GraphWeatherForecasterConfig:
 
 
 class GraphWeatherForecaster(AutoGraphModule, TopologyRecord, torch.nn.Module, PyTorchModelHubMixin):
-    """forecast.py:61-247 (the thermalizer is an optional extra outside the hot path; the constraint layer runs on
+    """forecast.py:61-247 (the thermalizer runs on csrc/gw_thermal.hip, the constraint layer on
     csrc/gw_constraint.hip)."""
 
     def __init__(self, lat_lons: list, resolution: int = 2, feature_dim: int = 78, aux_dim: int = 24,
@@ -162,11 +163,16 @@ class GraphWeatherForecaster(AutoGraphModule, TopologyRecord, torch.nn.Module, P
     def forward(self, features: torch.Tensor, t: int = 0) -> torch.Tensor:
         """forecast.py:215-247.  Fused path: data stays in the native layouts
         (dst-sorted shared graph, cached batch-independent embeddings) between encoder, processor and decoder.  In eval() under
-        no_grad() the call replays its own HIP graph from the third call of a shape on (graphed.AutoGraphModule)."""
+        no_grad() the call replays its own HIP graph from the third call of a shape on (graphed.AutoGraphModule).  ``t`` is the
+        thermalizer's timestep (ignored without one); a graph is only replayed at the timestep it was captured at."""
+        if self.use_thermalizer:
+            t = timestep(t, self.processor.thermalizer.timesteps)
+            y = self._auto_graph_step(features, t)
+            return y if y is not None else self._forward_eager(features, t)
         y = self._auto_graph_step(features)
         return y if y is not None else self._forward_eager(features)
 
-    def _forward_eager(self, features: torch.Tensor) -> torch.Tensor:
+    def _forward_eager(self, features: torch.Tensor, t: int = 0) -> torch.Tensor:
         if not features.is_cuda:
             raise RuntimeError("graph_weather_amd: features must be on a HIP device - there is no CPU path")
         if features.dtype != torch.float32:
@@ -175,7 +181,7 @@ class GraphWeatherForecaster(AutoGraphModule, TopologyRecord, torch.nn.Module, P
             raise RuntimeError("graph_weather_amd: features must be [B, nodes, >= %d channels]" % self.output_dim)
         features = features.contiguous()
         B, G = int(features.shape[0]), self.encoder.num_latlons
-        y = fused_forward(self.encoder, self.processor, self.decoder, features, features.reshape(B * G, features.shape[2]))
+        y = fused_forward(self.encoder, self.processor, self.decoder, features, features.reshape(B * G, features.shape[2]), t=t)
         if self.constraint_type != "none":
             # forecast.py:234-246: the output read as [B, H*W] grid rows, the input's first feature_dim channels as the
             # low-resolution reference (read in place through the features' row stride)

@@ -61,6 +61,7 @@ class ForwardGraph:
         self._mlps = None
         self._shaping = None
         self._graph: Optional[torch.cuda.CUDAGraph] = None
+        self._exposed = []
         self.input: Optional[torch.Tensor] = None
         self.output: Optional[torch.Tensor] = None
         self.captures = 0
@@ -84,11 +85,12 @@ class ForwardGraph:
         self._params = None
         self.pinned = False
 
-    def _eager(self, x: torch.Tensor) -> torch.Tensor:
+    def _eager(self, x: torch.Tensor, t=None) -> torch.Tensor:
         fwd = getattr(self.model, "_forward_eager", None)  # (models whose forward() may itself replay a graph: AutoGraph)
-        return fwd(x) if fwd is not None else self.model(x)
+        fwd = fwd if fwd is not None else self.model
+        return fwd(x) if t is None else fwd(x, t)  # (t: the thermalizer's timestep, part of the capture key)
 
-    def _state_key(self, shape, device, dtype) -> tuple:
+    def _state_key(self, shape, device, dtype, t=None) -> tuple:
         from .layers import MLP
 
         if self._params is None:  # (module structure is fixed after construction: walk it once; invalidate() re-walks)
@@ -99,9 +101,9 @@ class ForwardGraph:
         versions = tuple((p.data_ptr(), -1 if p.is_inference() else p._version) for p in self._params)
         dtypes = tuple(str(m.compute_dtype) for m in self._mlps)
         shaping = tuple(repr(getattr(m, a)) for m, a in self._shaping)
-        return (tuple(shape), str(device), str(dtype), versions, dtypes, shaping)
+        return (tuple(shape), str(device), str(dtype), versions, dtypes, shaping, t)
 
-    def _capture(self, features: torch.Tensor, pin: bool) -> None:
+    def _capture(self, features: torch.Tensor, pin: bool, t=None) -> None:
         from . import ops
 
         if ops.TIMER is not None:
@@ -119,13 +121,13 @@ class ForwardGraph:
         gc.collect()
         gc.disable()
         try:
-            self._capture_locked(features, pin, dev)
+            self._capture_locked(features, pin, dev, t)
         finally:
             if gc_was_on:
                 gc.enable()
         self.captures += 1
 
-    def _capture_locked(self, features: torch.Tensor, pin: bool, dev) -> None:
+    def _capture_locked(self, features: torch.Tensor, pin: bool, dev, t=None) -> None:
         with torch.inference_mode(False), torch.no_grad():
             if pin:
                 self.input = features  # the caller's buffer; the reference keeps its memory mapped for the graph's lifetime
@@ -138,14 +140,18 @@ class ForwardGraph:
             # belongs to the stream that will read it later (a side-stream warm-up left them owned by a stream nobody
             # synchronises with)
             for _ in range(max(1, self.warmup)):
-                self._eager(self.input)
+                self._eager(self.input, t)
             torch.cuda.synchronize(dev)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self.output = self._eager(self.input)
+                self.output = self._eager(self.input, t)
+            # buffers a module exposes for inspection (the thermalizer's ``last_noise``): the graph's own, handed back after
+            # every replay - an eager call in between leaves the module pointing at that call's tensor
+            self._exposed = [(weakref.ref(m), m.last_noise) for m in self.model.modules()
+                             if isinstance(getattr(m, "last_noise", None), torch.Tensor)]
         self._graph = g
 
-    def __call__(self, features: Optional[torch.Tensor] = None, clone: bool = False, pin_now: bool = False) -> torch.Tensor:
+    def __call__(self, features: Optional[torch.Tensor] = None, clone: bool = False, pin_now: bool = False, t=None) -> torch.Tensor:
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.model.parameters()) and self.model.training:
             raise RuntimeError("graph_weather_amd: ForwardGraph replays the inference forward - call it on model.eval() "
                                "(training steps go through autograd, which a static graph cannot follow)")
@@ -155,24 +161,28 @@ class ForwardGraph:
             features = self.input
         if not features.is_cuda:
             raise RuntimeError("graph_weather_amd: features must be on a HIP device - there is no CPU path")
-        key = self._state_key(features.shape, features.device, features.dtype)
+        key = self._state_key(features.shape, features.device, features.dtype, t)
         ptr = features.data_ptr()
         self._same_ptr = self._same_ptr + 1 if ptr == self._last_ptr else 1
         self._last_ptr = ptr
         if self._graph is None or key != self._key:
             # (pin_now: the caller has already seen this buffer on its previous calls - AutoGraph counts them while it runs eager)
             keep = self.pinned and self.input is not None and ptr == self.input.data_ptr()
-            self._capture(features, pin=(keep or (pin_now and self._pin_ok)) and features.is_contiguous())
+            self._capture(features, pin=(keep or (pin_now and self._pin_ok)) and features.is_contiguous(), t=t)
             self._key = key
         elif ptr != self.input.data_ptr():
             if self.pinned:  # a pinned graph reads somebody's buffer: never write into that - back to an own buffer, for good
                 self._pin_ok = False
-                self._capture(features, pin=False)
+                self._capture(features, pin=False, t=t)
             elif self._pin_ok and self.pin_after > 0 and self._same_ptr >= self.pin_after and features.is_contiguous():
-                self._capture(features, pin=True)  # the caller keeps handing over one buffer: read it in place
+                self._capture(features, pin=True, t=t)  # the caller keeps handing over one buffer: read it in place
             else:
                 self.input.copy_(features)
         self._graph.replay()
+        for ref, buf in self._exposed:
+            m = ref()
+            if m is not None:
+                m.last_noise = buf
         return self.output.clone() if clone else self.output
 
 
@@ -202,10 +212,10 @@ class AutoGraph:
                 and features.numel() * features.element_size() <= self.MAX_INPUT_BYTES and ops.TIMER is None
                 and not torch.cuda.is_current_stream_capturing())
 
-    def step(self, features: torch.Tensor) -> Optional[torch.Tensor]:
+    def step(self, features: torch.Tensor, t=None) -> Optional[torch.Tensor]:
         if not self.usable(features):
             return None
-        shape = (tuple(features.shape), features.dtype, features.device)
+        shape = (tuple(features.shape), features.dtype, features.device, t)  # (a new timestep counts afresh: eager first)
         if shape != self._shape:
             self._shape, self._seen = shape, 0
         self._seen += 1
@@ -216,7 +226,7 @@ class AutoGraph:
             return None
         if self._fg is None:
             self._fg = ForwardGraph(self._model_ref(), warmup=1, weak=True)
-        elif self._fg._graph is not None and self._fg._state_key(features.shape, features.device, features.dtype) != self._fg._key:
+        elif self._fg._graph is not None and self._fg._state_key(features.shape, features.device, features.dtype, t) != self._fg._key:
             # weights / dtype / flags changed under the graph: drop it and count afresh - a loop that alternates weight updates
             # and evaluation forwards must not pay a capture (three forwards' worth) per call
             self._fg._graph = None
@@ -225,7 +235,7 @@ class AutoGraph:
         try:
             # a buffer that came back on every call so far (a rollout's input, a staging buffer, a benchmark loop) is read in
             # place from the first capture on; fresh tensors per call get the graph's own input buffer and a copy per call
-            return self._fg(features, clone=True, pin_now=self._ptr_same > self.after)
+            return self._fg(features, clone=True, pin_now=self._ptr_same > self.after, t=t)
         except Exception as exc:  # a forward the capture cannot follow: say so once, stay eager from here on
             self.enabled = False
             self._fg = None
@@ -249,7 +259,7 @@ class AutoGraphModule:
         state.pop("_auto", None)  # a captured HIP graph is neither copied nor pickled with the module
         return state
 
-    def _auto_graph_step(self, features: torch.Tensor) -> Optional[torch.Tensor]:
+    def _auto_graph_step(self, features: torch.Tensor, t=None) -> Optional[torch.Tensor]:
         if not self.auto_graph:
             return None
         auto = self.__dict__.get("_auto")
@@ -258,4 +268,4 @@ class AutoGraphModule:
             auto = self.__dict__["_auto"] = AutoGraph(self)
         if not (features.is_cuda and features.dtype == torch.float32 and not self.training and not torch.is_grad_enabled()):
             return None
-        return auto.step(features)
+        return auto.step(features, t)

@@ -27,6 +27,7 @@ from . import wide
 from .autograd import OperandSpec
 from .graphs import ForecastGraphs, GraphPlan, build_forecast_graphs
 from .ops import BF16X3, Operand, PackedMLP
+from .thermalizer import ThermalizerLayer
 
 _NORMS = ["LayerNorm", "GraphNorm", "InstanceNorm", "BatchNorm", "MessageNorm"]
 
@@ -913,21 +914,31 @@ class Encoder(nn.Module):
 
 
 class Processor(nn.Module):
-    """``Processor`` - processor.py:17-128 (thermalizer not part of the hot path)."""
+    """``Processor`` - processor.py:17-128.  ``use_thermalizer``: ``ThermalizerLayer(input_dim)`` denoises the output rows
+    (thermalizer.py), as one image of all rows without efficient batching, per sample with it (processor.py:106-128)."""
 
     def __init__(self, input_dim: int = 256, edge_dim: int = 256, num_blocks: int = 9, hidden_dim_processor_node: int = 256,
                  hidden_dim_processor_edge: int = 256, hidden_layers_processor_node: int = 2,
                  hidden_layers_processor_edge: int = 2, mlp_norm_type: str = "LayerNorm", use_thermalizer: bool = False,
                  use_checkpointing: bool = False):
         super().__init__()
-        if use_thermalizer:
-            raise NotImplementedError("the thermalizer (reference default off, forecast.py:83) is outside the hot path")
         self.input_dim = input_dim
         self.use_thermalizer = use_thermalizer
         self.checkpoint_segments = 0
         self.graph_processor = GraphProcessor(num_blocks, input_dim, edge_dim, hidden_dim_processor_node,
                                               hidden_dim_processor_edge, hidden_layers_processor_node,
                                               hidden_layers_processor_edge, mlp_norm_type, use_checkpointing)
+        if use_thermalizer:
+            self.thermalizer = ThermalizerLayer(input_dim)
+
+    def thermalize(self, out: torch.Tensor, t, batch_size: int = 1, per_sample: bool = False) -> torch.Tensor:
+        """The thermalizer on the first ``input_dim`` columns of the processor's output rows [B * M, >= input_dim]: one image
+        of all rows (processor.py:125-127), or one image per sample (``per_sample``, processor.py:113-114)."""
+        x = out[:, :self.input_dim]
+        if not per_sample or batch_size <= 1:
+            return self.thermalizer(x, t)
+        n = int(x.shape[0]) // batch_size
+        return torch.cat([self.thermalizer(x[i * n:(i + 1) * n], t) for i in range(batch_size)])
 
     def set_checkpoint_segments(self, checkpoint_segments: int):
         """processor.py:70-81: 0 = per-block checkpointing as configured by ``use_checkpointing``; -1 = the whole processor
@@ -944,7 +955,8 @@ class Processor(nn.Module):
             x, edge_attr = x.contiguous(), edge_attr.contiguous()
         else:
             x, edge_attr = _pad256(x), _pad256(edge_attr)
-        if efficient_batching and batch_size is not None and batch_size > 1:
+        per_sample = efficient_batching and batch_size is not None and batch_size > 1
+        if per_sample:
             n = int(x.shape[0]) // batch_size
             plan = self.graph_processor._plan_for(edge_index, n)
             e_sorted = edge_attr[plan.perm].contiguous()
@@ -953,6 +965,8 @@ class Processor(nn.Module):
             plan = self.graph_processor._plan_for(edge_index, int(x.shape[0]))
             e_sorted = edge_attr[plan.perm].contiguous()
             out, _ = self.graph_processor.run_plan(x, plan, e_sorted, False, 1, False)
+        if self.use_thermalizer:
+            return self.thermalize(out, t, batch_size or 1, per_sample)
         return out if out.shape[1] == dn else out[:, :dn]
 
 
@@ -1148,19 +1162,21 @@ class AssimilatorDecoder(nn.Module):
 
 
 def fused_forward(encoder: "Encoder", processor: "Processor", decoder: "AssimilatorDecoder", features: torch.Tensor,
-                  residual: torch.Tensor) -> torch.Tensor:
+                  residual: torch.Tensor, t=0) -> torch.Tensor:
     """encoder -> processor -> decoder of the forecaster / GraphCast wrapper in native layouts.  Inference: every node update
     also makes the layer-1 node products (and zero-fills the aggregate) of the block that follows it - the encoder's for the
     first processor block, each processor block's for the next, the last one's for the decoder - so no projection launch runs
-    between blocks.  Under autograd the blocks keep their separate differentiable projections."""
+    between blocks.  Under autograd the blocks keep their separate differentiable projections.  A processor with a
+    thermalizer takes the unfused chain with the thermalizer (at timestep ``t``) between processor and decoder: the decoder
+    projects the denoised rows itself."""
     B = int(features.shape[0])
     gp = processor.graph_processor
     if wide.encoder_is_wide(encoder) or wide.processor_is_wide(gp) or wide.decoder_is_wide(decoder):
-        return wide.forward(encoder, processor, decoder, features, residual)
+        return wide.forward(encoder, processor, decoder, features, residual, t=t)
     _, lat_plan = encoder._plans(features.device)
     e_lat = encoder.latent_edge_embedding(lat_plan)
     fuse = (not _autograd_on(encoder, features) and not _autograd_on(gp) and not _autograd_on(decoder) and len(gp.blocks) > 0
-            and gp.checkpoint_segments == 0)
+            and gp.checkpoint_segments == 0 and not processor.use_thermalizer)
     if fuse:
         enc_n = encoder.graph_processor.blocks[0].node_model.node_mlp.packed()
         first = gp.blocks[0].edge_model.edge_mlp.packed()
@@ -1170,6 +1186,8 @@ def fused_forward(encoder: "Encoder", processor: "Processor", decoder: "Assimila
     if not fuse:
         x = encoder.encode(features)
         x, _ = gp.run_plan(x, lat_plan, e_lat, True, B, False)
+        if processor.use_thermalizer:
+            x = processor.thermalize(x, t)  # forecast.py:227: the B * M rows as one image (efficient_batching=False)
         return decoder.decode(x, B, residual=residual)
     dec_prefetch = decoder.prefetch_tables(features.device)  # cold forward: the decoder's big tables on a side stream
 

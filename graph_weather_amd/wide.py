@@ -535,10 +535,12 @@ def decode(dec, processor_features: torch.Tensor, batch_size: int, residual: Opt
     return y.reshape(B, G, dec.output_dim)
 
 
-def forward(encoder, processor, decoder, features: torch.Tensor, residual: torch.Tensor) -> torch.Tensor:
-    """forecast.py:226-228 for a model any of whose parts is wider than the fused kernels."""
+def forward(encoder, processor, decoder, features: torch.Tensor, residual: torch.Tensor, t=0) -> torch.Tensor:
+    """forecast.py:226-228 for a model any of whose parts is wider than the fused kernels (``t``: the thermalizer's timestep)."""
     B = int(features.shape[0])
     _, lat_plan = encoder._plans(features.device)
     x = encode(encoder, features)
     x, _ = run_blocks(processor.graph_processor, x, lat_plan, latent_edges(encoder, lat_plan), True, B, False)
+    if processor.use_thermalizer:
+        x = processor.thermalize(x, t)
     return decode(decoder, x, B, residual=residual)

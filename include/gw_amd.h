@@ -496,6 +496,102 @@ int gw_constraint_forward(const gw_constraint_args* a, void* workspace, size_t w
 int gw_constraint_backward(const gw_constraint_args* a, const float* dout, int32_t ld_dout, void* workspace, size_t workspace_bytes,
                            float* dhr, int32_t ld_dhr, float* dlr, int32_t ld_dlr, void* stream);
 
+/* =====================================================================================================================
+ * ThermalizerLayer / AdaptiveUNet (graph_weather/models/layers/thermalizer.py), csrc/gw_thermal.hip.  Activations are NHWC
+ * pixel rows: row (b * H + y) * W + x of an image batch, `channels` floats, row stride ld.  Everything is fp32.
+ *
+ * gw_thermal_conv_forward is an implicit GEMM on v_mfma_f32_16x16x4_f32 over GEMM pixels q = (b, qy, qx) of a q_h x q_w
+ * grid per image:
+ *   out[b, out_scale * q + out_off, co] = bias[co] + sum over live taps (ty, tx) and ci < cin of
+ *                                         A(b, in_scale * q + in_off(ty, tx), ci) * w[wy * w_stride_y + wx * w_stride_x
+ *                                                                                   + ci * w_stride_ci + co * w_stride_co]
+ * with (wy, wx) = the taps' w_idx.  Input pixels outside in_h x in_w read zero.  One mapping serves Conv2d (stride 1), its
+ * input gradient (flipped, transposed weight strides), the four output-parity sub-convolutions of
+ * ConvTranspose2d(3, stride 2, pad 1, output_padding 1) and that transpose's input gradient (in_scale 2).  Taps that can
+ * never hit the image are left out of the lists by the caller.
+ *   a_mode GW_THERMAL_A_PLAIN    A = a[row * ld_a + ci]
+ *          GW_THERMAL_A_GN_RELU  A = max(a * a_scale[b, ci] + a_shift[b, ci], 0)   (GroupNorm + ReLU on load)
+ *          GW_THERMAL_A_DIFFUSE  A = sa * x + s1 * eps for ci < features (x = a rows, eps [rows, features] dense),
+ *                                ci == features: x-coordinate linspace(0, 1, in_w), ci == features + 1: linspace(0, 1, in_h)
+ *   e_mode GW_THERMAL_E_STORE    out[row * ld_out + co] = acc + bias
+ *          GW_THERMAL_E_DIFFUSE  out[row * ld_out + co] = (noisy - s1 * (acc + bias)) / sa, noisy = sa * x + s1 * eps from
+ *                                x [row * ld_x + co] and eps [row * features + co]
+ * gw_thermal_conv_wgrad reads the same arguments with `out` as the output gradient G and writes
+ *   dw[wy, wx, ci, co] (through the w strides) = sum_q A(q, tap, ci) * G(out pixel of q, co)
+ * for the live taps only (dead taps keep what dw held), by per-tap TN products over fixed pixel slabs whose partials are
+ * summed in one fixed order: bitwise reproducible, no atomics. */
+#define GW_THERMAL_MAX_TAPS 7
+#define GW_THERMAL_A_PLAIN 0
+#define GW_THERMAL_A_GN_RELU 1
+#define GW_THERMAL_A_DIFFUSE 2
+#define GW_THERMAL_E_STORE 0
+#define GW_THERMAL_E_DIFFUSE 1
+typedef struct gw_thermal_taps {
+  int32_t n;                              /* live taps along this axis, 1..GW_THERMAL_MAX_TAPS */
+  int32_t in_off[GW_THERMAL_MAX_TAPS];    /* input coordinate = in_scale * q + in_off[t] */
+  int32_t w_idx[GW_THERMAL_MAX_TAPS];     /* weight index of tap t along this axis */
+} gw_thermal_taps;
+typedef struct gw_thermal_conv_args {
+  int32_t batch, in_h, in_w, out_h, out_w, q_h, q_w;
+  int32_t in_scale_h, in_scale_w, out_scale_h, out_scale_w, out_off_h, out_off_w;
+  gw_thermal_taps ty, tx;
+  int32_t cin, cout;
+  int32_t a_mode, e_mode;
+  const float* a;
+  int32_t ld_a, features;                 /* features: the diffusion modes' F */
+  const float* a_scale;                   /* [batch, cin] (GN_RELU) */
+  const float* a_shift;
+  const float* w;
+  int64_t w_stride_y, w_stride_x, w_stride_ci, w_stride_co;
+  const float* bias;                      /* [cout] or NULL */
+  float* out;
+  int32_t ld_out, ld_x;
+  const float* x;                         /* E_DIFFUSE: the clean rows */
+  const float* eps;                       /* diffusion modes: the noise rows [rows, features] */
+  float sa, s1;                           /* sqrt(alpha_bar_t), sqrt(1 - alpha_bar_t) */
+} gw_thermal_conv_args;
+int gw_thermal_conv_forward(const gw_thermal_conv_args* a, void* stream);
+size_t gw_thermal_conv_wgrad_workspace_bytes(const gw_thermal_conv_args* a);
+int gw_thermal_conv_wgrad(const gw_thermal_conv_args* a, void* workspace, size_t workspace_bytes, float* dw, void* stream);
+/* out[c] = sum over rows of g[r * ld + c] (bias gradients), slab partials summed in one fixed order. */
+size_t gw_thermal_colsum_workspace_bytes(int64_t rows, int32_t cols);
+int gw_thermal_colsum(int64_t rows, int32_t cols, const float* g, int32_t ld, void* workspace, size_t workspace_bytes, float* out,
+                      void* stream);
+/* GroupNorm(groups, channels) over images of hw pixels.  Statistics: per-slab (count, mean, M2) partials merged in one fixed
+ * order (Chan); stats[b, g] = (mean, rstd); scale / shift [batch, channels] = the affine the consumer applies on load
+ * (gamma * rstd, beta - mean * gamma * rstd).  The backward takes dy = the gradient of relu(GroupNorm(x)) and writes dx
+ * [rows, channels] dense, dgamma and dbeta. */
+size_t gw_thermal_groupnorm_workspace_bytes(int32_t batch, int32_t hw, int32_t channels, int32_t groups);
+int gw_thermal_groupnorm_forward(int32_t batch, int32_t hw, int32_t channels, int32_t groups, const float* x, int32_t ld_x,
+                                 const float* gamma, const float* beta, float eps, void* workspace, size_t workspace_bytes,
+                                 float* stats, float* scale, float* shift, void* stream);
+int gw_thermal_groupnorm_backward(int32_t batch, int32_t hw, int32_t channels, int32_t groups, const float* x, int32_t ld_x,
+                                  const float* scale, const float* shift, const float* stats, const float* gamma, const float* dy,
+                                  int32_t ld_dy, void* workspace, size_t workspace_bytes, float* dx, float* dgamma, float* dbeta,
+                                  void* stream);
+/* MaxPool2d(3, 2, 1) of relu(x * scale + shift) (scale / shift [batch, channels]) -> out rows (ld_out) and the argmax
+ * (pixel index y * w + x inside the image, first maximum in window order) idx [out rows, channels].  The backward gathers
+ * (g1 + g2) (g2 may be NULL) at each input pixel from the <= 2 x 2 windows that hold it -> dx [rows, channels] dense. */
+int gw_thermal_maxpool_forward(int32_t batch, int32_t h, int32_t w, int32_t channels, const float* x, int32_t ld_x,
+                               const float* scale, const float* shift, float* out, int32_t ld_out, int32_t* idx, void* stream);
+int gw_thermal_maxpool_backward(int32_t batch, int32_t h, int32_t w, int32_t channels, const int32_t* idx, const float* g1,
+                                int32_t ld_g1, const float* g2, int32_t ld_g2, float* dx, void* stream);
+/* Bilinear resize (interpolate(mode="bilinear", align_corners=False)) of h_in x w_in images to h_out x w_out; the backward is
+ * a gather over the output pixels that read each input pixel (no atomics) -> dx [rows_in, channels] dense. */
+int gw_thermal_resize_forward(int32_t batch, int32_t h_in, int32_t w_in, int32_t h_out, int32_t w_out, int32_t channels,
+                              const float* x, int32_t ld_x, float* out, int32_t ld_out, void* stream);
+int gw_thermal_resize_backward(int32_t batch, int32_t h_in, int32_t w_in, int32_t h_out, int32_t w_out, int32_t channels,
+                               const float* g, int32_t ld_g, float* dx, void* stream);
+/* Row-wise ends of the diffusion step, over rows x features:
+ *   GW_THERMAL_ROWS_FINALIZE  out = (sa * p + s1 * q - s1 * r) / sa   (p = x rows, q = eps rows, r = predicted noise rows)
+ *   GW_THERMAL_ROWS_SCALE     out = sa * p                            (sa carries the factor)
+ *   GW_THERMAL_ROWS_AXPY      out = p + sa * q */
+#define GW_THERMAL_ROWS_FINALIZE 0
+#define GW_THERMAL_ROWS_SCALE 1
+#define GW_THERMAL_ROWS_AXPY 2
+int gw_thermal_rows(int32_t mode, int64_t rows, int32_t features, float sa, float s1, const float* p, int32_t ld_p, const float* q,
+                    int32_t ld_q, const float* r, int32_t ld_r, float* out, int32_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
