@@ -15,6 +15,8 @@ import torch
 
 # from graph_weather import GraphWeatherForecaster                      # reference
 # from graph_weather.models.losses import NormalizedMSELoss             # reference
+# (AMSENormalizedLoss, the reference's spherical-harmonic loss, is there too and needs no torch_harmonics:
+#  AMSENormalizedLoss(variance).cuda()(pred.reshape(b, h, w, c).permute(0, 3, 1, 2), target_grid).backward())
 from graph_weather_amd import AdamW, GraphWeatherForecaster, NormalizedMSELoss, rollout  # MI355X-native
 
 

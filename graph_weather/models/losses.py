@@ -1,2 +1,2 @@
-"""graph_weather/models/losses.py of the reference (the hot path's loss only)."""
-from graph_weather_amd.losses import NormalizedMSELoss  # noqa: F401
+"""graph_weather/models/losses.py of the reference: both of its losses."""
+from graph_weather_amd.losses import AMSENormalizedLoss, NormalizedMSELoss  # noqa: F401

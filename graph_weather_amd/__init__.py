@@ -2,7 +2,7 @@
 
 Mirrors the import surface of the reference for that path (``graph_weather/__init__.py:9``,
 ``graph_weather/models/__init__.py:13-15``): ``GraphWeatherForecaster``, ``Encoder``, ``Processor``, ``Decoder``,
-``GraphProcessor``, ``MLP``, ``NormalizedMSELoss``.
+``GraphProcessor``, ``MLP``, ``NormalizedMSELoss``, ``AMSENormalizedLoss``.
 """
 from .analysis import AssimilatorEncoder, GraphWeatherAssimilator, GraphWeatherAssimilatorConfig  # noqa: F401
 from .forecast import GraphWeatherForecaster, GraphWeatherForecasterConfig  # noqa: F401
@@ -21,7 +21,7 @@ from .layers import (  # noqa: F401
 )
 from .ops import BF16X3  # noqa: F401  (set_compute_dtype(model, BF16X3): split-operand products, csrc/gw_split.hip)
 from .graphcast import GraphCast, GraphCastConfig  # noqa: F401
-from .losses import NormalizedMSELoss  # noqa: F401
+from .losses import AMSENormalizedLoss, NormalizedMSELoss  # noqa: F401  (AMSE: csrc/gw_sht.hip)
 from .regional import (  # noqa: F401
     BoundaryNudgingLayer,
     DynamicGraphBuilder,

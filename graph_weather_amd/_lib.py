@@ -33,6 +33,8 @@ EXPORTS = [
     "gw_thermal_colsum", "gw_thermal_groupnorm_workspace_bytes", "gw_thermal_groupnorm_forward", "gw_thermal_groupnorm_backward",
     "gw_thermal_maxpool_forward", "gw_thermal_maxpool_backward", "gw_thermal_resize_forward", "gw_thermal_resize_backward",
     "gw_thermal_rows",
+    "gw_amse_mmax", "gw_amse_dft_rows", "gw_amse_legendre_floats", "gw_amse_coeff_floats", "gw_amse_workspace_bytes",
+    "gw_amse_forward", "gw_amse_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -282,6 +284,22 @@ def lib():
     L.gw_thermal_rows.restype = c_int
     L.gw_thermal_rows.argtypes = [c_int32, c_int64, c_int32, c_float, c_float, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                   c_void_p, c_int32, c_void_p]
+    L.gw_amse_mmax.restype = c_int32
+    L.gw_amse_mmax.argtypes = [c_int32, c_int32]
+    L.gw_amse_dft_rows.restype = c_int32
+    L.gw_amse_dft_rows.argtypes = [c_int32, c_int32]
+    L.gw_amse_legendre_floats.restype = c_size_t
+    L.gw_amse_legendre_floats.argtypes = [c_int32, c_int32]
+    L.gw_amse_coeff_floats.restype = c_size_t
+    L.gw_amse_coeff_floats.argtypes = [c_int32, c_int32, c_int32]
+    L.gw_amse_workspace_bytes.restype = c_size_t
+    L.gw_amse_workspace_bytes.argtypes = [c_int32, c_int32, c_int32, c_int32]
+    L.gw_amse_forward.restype = c_int
+    L.gw_amse_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  ctypes.c_double, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_amse_backward.restype = c_int
+    L.gw_amse_backward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   c_void_p, c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

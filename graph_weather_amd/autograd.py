@@ -689,3 +689,20 @@ class NormalizedMSEFunction(torch.autograd.Function):
                                                    1 if (ctx.has_var and iv.numel() == pred.numel()) else 0, w.data_ptr(), int(w.numel()), b, nodes, c, dl.data_ptr(), dpred.data_ptr(),
                                                    _st(pred)), "gw_normalized_mse_backward")
         return dpred, None, None, None
+
+
+class AMSENormalizedFunction(torch.autograd.Function):
+    """``AMSENormalizedLoss.forward`` (losses.py:142-195): the forward saves the spherical-harmonic coefficients and the two
+    per-(field, degree) factors, the backward runs the adjoint transform on ``2 g_pp a + g_num b``."""
+
+    @staticmethod
+    def forward(ctx, pred, target, variance, epsilon):
+        loss, coeff, gfac = ops.amse_forward(pred, target, variance, epsilon, save=True)
+        ctx.save_for_backward(coeff, gfac)
+        ctx.shape = tuple(pred.shape)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        coeff, gfac = ctx.saved_tensors
+        return ops.amse_backward(coeff, gfac, dloss.reshape(1).contiguous().float(), ctx.shape), None, None, None

@@ -471,3 +471,75 @@ def normalized_mse_forward(pred: torch.Tensor, target: torch.Tensor, lat_weights
                                                         int(lat_weights.numel()), b, nodes, c, loss.data_ptr(), _stream(pred)),
                    "gw_normalized_mse_forward")
     return loss
+
+
+_AMSE_TABLES: dict = {}
+
+
+def amse_tables(nlat: int, nlon: int, device: torch.device):
+    """Device tables of the spherical-harmonic transform (``sht_tables.device_tables``), built once per
+    ``(nlat, nlon, device)`` on the host in float64 and uploaded as float32."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(nlat), int(nlon), device)
+    hit = _AMSE_TABLES.get(key)
+    if hit is None:
+        from . import sht_tables
+
+        need = sht_tables.table_bytes(nlat, nlon)
+        free, _ = torch.cuda.mem_get_info(device)
+        if need > free:
+            raise RuntimeError("graph_weather_amd: the spherical-harmonic tables of a %d x %d grid need %d bytes of device memory, "
+                               "%d are free" % (nlat, nlon, need, free))
+        dft, leg = sht_tables.device_tables(nlat, nlon)
+        hit = (torch.from_numpy(dft).to(device), torch.from_numpy(leg).to(device))
+        _AMSE_TABLES[key] = hit
+    return hit
+
+
+def amse_forward(pred: torch.Tensor, target: torch.Tensor, variance: torch.Tensor, epsilon: float, save: bool = False,
+                 clear: bool = False):
+    """``AMSENormalizedLoss.forward`` (losses.py:142-195) on [B, C, H, W] fields.  Returns the scalar loss, and with
+    ``save`` also the coefficients [4, mmax, lmax, B * C] (pred re / im, target re / im; ``clear`` zeroes the entries with
+    l < m, which the kernels neither write nor read) and the two gradient factors [2, lmax, B * C] the backward reads."""
+    _require(pred, "pred")
+    _require(target, "target")
+    _require(variance, "feature_variance")
+    b, c, nlat, nlon = (int(s) for s in pred.shape)
+    if variance.numel() != c:
+        raise RuntimeError("graph_weather_amd: feature_variance must hold one value per channel (%d), got %d" % (c, variance.numel()))
+    L = _lib.lib()
+    n = b * c
+    dft, leg = amse_tables(nlat, nlon, pred.device)
+    ws = torch.empty(L.gw_amse_workspace_bytes(n, nlat, nlon, 0), dtype=torch.uint8, device=pred.device)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    coeff = gfac = None
+    if save:
+        mmax = L.gw_amse_mmax(nlat, nlon)
+        coeff = (torch.zeros if clear else torch.empty)((4, mmax, nlat, n), dtype=torch.float32, device=pred.device)
+        gfac = torch.empty((2, nlat, n), dtype=torch.float32, device=pred.device)
+    with on_device_of(pred):
+        _lib.check(L.gw_amse_forward(n, c, nlat, nlon, pred.data_ptr(), target.data_ptr(), dft.data_ptr(), leg.data_ptr(),
+                                     variance.data_ptr(), float(epsilon), ws.data_ptr(), ws.numel(),
+                                     None if coeff is None else coeff.data_ptr(), None if gfac is None else gfac.data_ptr(),
+                                     loss.data_ptr(), _stream(pred)), "gw_amse_forward")
+    return (loss, coeff, gfac) if save else loss
+
+
+def amse_backward(coeff: torch.Tensor, gfac: torch.Tensor, dloss: torch.Tensor, shape) -> torch.Tensor:
+    """Gradient of ``amse_forward`` with respect to ``pred`` ([B, C, H, W] dense)."""
+    b, c, nlat, nlon = (int(s) for s in shape)
+    _require(coeff, "coeff")
+    _require(gfac, "gfac")
+    _require(dloss, "dloss")
+    L = _lib.lib()
+    n = b * c
+    dft, leg = amse_tables(nlat, nlon, coeff.device)
+    ws = torch.empty(L.gw_amse_workspace_bytes(n, nlat, nlon, 1), dtype=torch.uint8, device=coeff.device)
+    dpred = torch.empty((b, c, nlat, nlon), dtype=torch.float32, device=coeff.device)
+    with on_device_of(coeff):
+        _lib.check(L.gw_amse_backward(n, nlat, nlon, coeff.data_ptr(), gfac.data_ptr(), dloss.data_ptr(), dft.data_ptr(),
+                                      leg.data_ptr(), ws.data_ptr(), ws.numel(), dpred.data_ptr(), _stream(coeff)),
+                   "gw_amse_backward")
+    return dpred

@@ -592,6 +592,32 @@ int gw_thermal_resize_backward(int32_t batch, int32_t h_in, int32_t w_in, int32_
 int gw_thermal_rows(int32_t mode, int64_t rows, int32_t features, float sa, float s1, const float* p, int32_t ld_p, const float* q,
                     int32_t ld_q, const float* r, int32_t ld_r, float* out, int32_t ld_out, void* stream);
 
+/* =====================================================================================================================
+ * AMSENormalizedLoss (graph_weather/models/losses.py:98-195), csrc/gw_sht.hip: the orthonormal real spherical-harmonic
+ * transform on the equiangular grid (nlat Clenshaw-Curtis latitudes with both poles, nlon longitudes) as two dense fp32
+ * MFMA products with the loss fused behind the second.  lmax = nlat, mmax = min(nlat, nlon / 2 + 1) = gw_amse_mmax.
+ * pred / target are `fields` = B * C dense [nlat, nlon] images each (field n has channel n % channels).  Host-built tables:
+ *   dft       [gw_amse_dft_rows, nlon]: row c * rows / 2 + m holds (2 pi / nlon) * cos(2 pi m j / nlon) for c = 0 and
+ *             -(2 pi / nlon) * sin(...) for c = 1, m < mmax; the other rows are zero
+ *   legendre  gw_amse_legendre_floats floats: order m starts at (m * lmax - m (m - 1) / 2) * nlat and holds the rows
+ *             l = m .. lmax - 1 of Pbar_l^m(cos theta_k) * w_k, nlat floats each (degrees l < m are not stored)
+ * gw_amse_forward writes the scalar loss.  With coeff / gfac given (both or neither) it also saves what the backward reads:
+ *   coeff [4, mmax, lmax, fields]  pred re, pred im, target re, target im of a[n, l, m]; entries with l < m are not written
+ *   gfac  [2, lmax, fields]        d term / d pp and d term / d num, times 1 / (fields * (variance + epsilon))
+ * gw_amse_backward writes dpred [fields, nlat, nlon] = dloss[0] * d loss / d pred.  The per-(n, l) sums and the loss terms
+ * are combined in fp64 in one fixed order; no atomics, no host synchronisation.  The queries need no GPU. */
+int32_t gw_amse_mmax(int32_t nlat, int32_t nlon);
+int32_t gw_amse_dft_rows(int32_t nlat, int32_t nlon);
+size_t gw_amse_legendre_floats(int32_t nlat, int32_t nlon);
+size_t gw_amse_coeff_floats(int32_t fields, int32_t nlat, int32_t nlon);
+/* backward = 0: bytes gw_amse_forward needs, else gw_amse_backward (0 with the error set on bad arguments). */
+size_t gw_amse_workspace_bytes(int32_t fields, int32_t nlat, int32_t nlon, int32_t backward);
+int gw_amse_forward(int32_t fields, int32_t channels, int32_t nlat, int32_t nlon, const float* pred, const float* target,
+                    const float* dft, const float* legendre, const float* variance, double epsilon, void* workspace,
+                    size_t workspace_bytes, float* coeff, float* gfac, float* loss, void* stream);
+int gw_amse_backward(int32_t fields, int32_t nlat, int32_t nlon, const float* coeff, const float* gfac, const float* dloss,
+                     const float* dft, const float* legendre, void* workspace, size_t workspace_bytes, float* dpred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
