@@ -9,4 +9,5 @@ from graph_weather_amd import (  # noqa: F401
     Processor,
     RegionalForecaster,
     RegionalForecasterConfig,
+    StochasticDecompositionLayer,
 )

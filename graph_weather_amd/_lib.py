@@ -35,6 +35,7 @@ EXPORTS = [
     "gw_thermal_rows",
     "gw_amse_mmax", "gw_amse_dft_rows", "gw_amse_legendre_floats", "gw_amse_coeff_floats", "gw_amse_workspace_bytes",
     "gw_amse_forward", "gw_amse_backward",
+    "gw_modulate_workspace_bytes", "gw_sdl_forward", "gw_sdl_backward", "gw_film_forward", "gw_film_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -300,6 +301,18 @@ def lib():
     L.gw_amse_backward.restype = c_int
     L.gw_amse_backward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                    c_void_p, c_void_p]
+    L.gw_modulate_workspace_bytes.restype = c_size_t
+    L.gw_modulate_workspace_bytes.argtypes = [c_int64, c_int64]
+    L.gw_sdl_forward.restype = c_int
+    L.gw_sdl_forward.argtypes = [c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_sdl_backward.restype = c_int
+    L.gw_sdl_backward.argtypes = [c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p, c_void_p, c_void_p]
+    L.gw_film_forward.restype = c_int
+    L.gw_film_forward.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_film_backward.restype = c_int
+    L.gw_film_backward.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

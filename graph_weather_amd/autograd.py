@@ -706,3 +706,34 @@ class AMSENormalizedFunction(torch.autograd.Function):
     def backward(ctx, dloss):
         coeff, gfac = ctx.saved_tensors
         return ops.amse_backward(coeff, gfac, dloss.reshape(1).contiguous().float(), ctx.shape), None, None, None
+
+
+class StochasticDecompositionFunction(torch.autograd.Function):
+    """x + (alpha * style) * eps (csrc/gw_modulate.hip).  The backward regenerates eps from the 8-byte key: only the key, style
+    and alpha are saved (with ``noise`` given, that tensor instead of the key).  The gradient of x is the incoming one."""
+
+    @staticmethod
+    def forward(ctx, x, style, alpha, key, noise):
+        ctx.save_for_backward(style, alpha, key, noise)
+        return ops.sdl_forward(x, style, alpha, key, noise)
+
+    @staticmethod
+    def backward(ctx, dout):
+        style, alpha, key, noise = ctx.saved_tensors
+        d_style, d_alpha = ops.sdl_backward(dout.contiguous(), style, alpha, key, noise, ctx.needs_input_grad[1],
+                                            ctx.needs_input_grad[2])
+        return (dout if ctx.needs_input_grad[0] else None), d_style, d_alpha, None, None
+
+
+class FiLMFunction(torch.autograd.Function):
+    """x * gamma + beta (csrc/gw_modulate.hip); dx = dout * gamma, d_gamma = sum_s dout * x, d_beta = sum_s dout in one pass."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta):
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, gamma)
+        return ops.film_forward(x, gamma, beta)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, gamma = ctx.saved_tensors
+        return ops.film_backward(dout.contiguous(), x, gamma, *ctx.needs_input_grad)

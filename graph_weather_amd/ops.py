@@ -543,3 +543,103 @@ def amse_backward(coeff: torch.Tensor, gfac: torch.Tensor, dloss: torch.Tensor, 
                                       leg.data_ptr(), ws.data_ptr(), ws.numel(), dpred.data_ptr(), _stream(coeff)),
                    "gw_amse_backward")
     return dpred
+
+
+def _modulate_rows(x: torch.Tensor) -> Tuple[int, int, int]:
+    """(rows, channels, spatial) of a dense [B, C, *spatial] tensor as csrc/gw_modulate.hip reads it."""
+    rows, channels = int(x.shape[0]) * int(x.shape[1]), int(x.shape[1])
+    return rows, channels, (x.numel() // rows if rows else 0)
+
+
+def sdl_key(device) -> torch.Tensor:
+    """A fresh 64-bit noise key in device memory, drawn from torch's own generator of ``device``: ``torch.manual_seed``
+    fixes it, successive draws differ, a captured graph draws a new one on every replay, and the host never reads it."""
+    return torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64, device=device)
+
+
+def sdl_noise(key: torch.Tensor, shape) -> torch.Tensor:
+    """eps(key, i) of include/gw_amd.h for the flat indices of a dense tensor of ``shape``: the values the stochastic
+    decomposition layer draws under ``key`` (one int64 on the device)."""
+    _require(key, "key", torch.int64)
+    out = torch.empty(tuple(int(s) for s in shape), dtype=torch.float32, device=key.device)
+    if out.numel():
+        with on_device_of(out):
+            _lib.check(_lib.lib().gw_sdl_forward(out.numel(), 1, 1, None, None, None, key.data_ptr(), None, out.data_ptr(),
+                                                 _stream(out)), "gw_sdl_forward")
+    return out
+
+
+def sdl_forward(x: torch.Tensor, style: torch.Tensor, alpha: torch.Tensor, key: Optional[torch.Tensor],
+                noise: Optional[torch.Tensor]) -> torch.Tensor:
+    """stochastic_decomposition.py:56-68: x + (alpha[c] * style[b, c]) * eps, eps = ``noise`` or eps(key, flat index)."""
+    _require(x, "x")
+    _require(style, "style")
+    _require(alpha, "alpha")
+    rows, channels, spatial = _modulate_rows(x)
+    if style.numel() != rows or alpha.numel() != channels:
+        raise RuntimeError("graph_weather_amd: style must be [B, C] and alpha hold C values for x [B, C, ...]")
+    if noise is not None:
+        _require(noise, "noise")
+        if noise.shape != x.shape:
+            raise RuntimeError("graph_weather_amd: noise must be shaped like x")
+    else:
+        _require(key, "key", torch.int64)
+    out = torch.empty_like(x)
+    if x.numel():
+        with on_device_of(x):
+            _lib.check(_lib.lib().gw_sdl_forward(rows, channels, spatial, x.data_ptr(), style.data_ptr(), alpha.data_ptr(),
+                                                 None if key is None else key.data_ptr(),
+                                                 None if noise is None else noise.data_ptr(), out.data_ptr(), _stream(x)),
+                       "gw_sdl_forward")
+    return out
+
+
+def sdl_backward(dy: torch.Tensor, style: torch.Tensor, alpha: torch.Tensor, key: Optional[torch.Tensor],
+                 noise: Optional[torch.Tensor], want_style: bool, want_alpha: bool):
+    """(d_style [B, C], d_alpha shaped like alpha) of ``sdl_forward``; the gradient of x is ``dy`` itself."""
+    _require(dy, "dy")
+    rows, channels, spatial = _modulate_rows(dy)
+    d_style = torch.empty_like(style) if want_style else None
+    d_alpha = torch.empty_like(alpha) if want_alpha else None
+    if (want_style or want_alpha) and dy.numel():
+        L = _lib.lib()
+        ws = torch.empty(L.gw_modulate_workspace_bytes(rows, spatial), dtype=torch.uint8, device=dy.device)
+        with on_device_of(dy):
+            _lib.check(L.gw_sdl_backward(rows, channels, spatial, dy.data_ptr(), style.data_ptr(), alpha.data_ptr(),
+                                         None if key is None else key.data_ptr(), None if noise is None else noise.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), None if d_style is None else d_style.data_ptr(),
+                                         None if d_alpha is None else d_alpha.data_ptr(), _stream(dy)), "gw_sdl_backward")
+    return d_style, d_alpha
+
+
+def film_forward(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
+    """film.py:72-75: x * gamma[b, c] + beta[b, c] over every trailing dimension of x [B, C, ...]."""
+    _require(x, "x")
+    _require(gamma, "gamma")
+    _require(beta, "beta")
+    rows, _, spatial = _modulate_rows(x)
+    if gamma.numel() != rows or beta.numel() != rows:
+        raise RuntimeError("graph_weather_amd: gamma and beta must be [B, C] for x [B, C, ...]")
+    out = torch.empty_like(x)
+    if x.numel():
+        with on_device_of(x):
+            _lib.check(_lib.lib().gw_film_forward(rows, spatial, x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), out.data_ptr(),
+                                                  _stream(x)), "gw_film_forward")
+    return out
+
+
+def film_backward(dy: torch.Tensor, x: torch.Tensor, gamma: torch.Tensor, want_x: bool, want_gamma: bool, want_beta: bool):
+    """(dx, d_gamma, d_beta) of ``film_forward``."""
+    _require(dy, "dy")
+    rows, _, spatial = _modulate_rows(dy)
+    dx = torch.empty_like(dy) if want_x else None
+    d_gamma = torch.empty_like(gamma) if want_gamma else None
+    d_beta = torch.empty_like(gamma) if want_beta else None
+    if (want_x or want_gamma or want_beta) and dy.numel():
+        L = _lib.lib()
+        ws = torch.empty(L.gw_modulate_workspace_bytes(rows, spatial), dtype=torch.uint8, device=dy.device)
+        with on_device_of(dy):
+            _lib.check(L.gw_film_backward(rows, spatial, dy.data_ptr(), None if x is None else x.data_ptr(), gamma.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          None if dx is None else dx.data_ptr(), None if d_gamma is None else d_gamma.data_ptr(),
+                                          None if d_beta is None else d_beta.data_ptr(), _stream(dy)), "gw_film_backward")
+    return dx, d_gamma, d_beta

@@ -618,6 +618,35 @@ int gw_amse_forward(int32_t fields, int32_t channels, int32_t nlat, int32_t nlon
 int gw_amse_backward(int32_t fields, int32_t nlat, int32_t nlon, const float* coeff, const float* gfac, const float* dloss,
                      const float* dft, const float* legendre, void* workspace, size_t workspace_bytes, float* dpred, void* stream);
 
+/* =====================================================================================================================
+ * Per-channel modulation of [B, C, *spatial] activations, csrc/gw_modulate.hip: StochasticDecompositionLayer
+ * (graph_weather/models/layers/stochastic_decomposition.py) and FiLMApplier (layers/film.py).  A tensor is `rows` = B * C
+ * dense rows of `spatial` floats; row r has channel r % channels.  One streaming pass each way, no atomics, no host
+ * synchronisation; reductions run in one fixed order (bitwise reproducible).
+ *
+ * The noise eps(key, i) is a pure function of a 64-bit key (two 32-bit words in DEVICE memory, low word first; never read
+ * on the host) and the flat element index i - not of launch geometry or vector width:
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (lo32(i / 4), hi32(i / 4), 0, 0), key) serve elements 4j .. 4j + 3;
+ *   u = ((w >> 8) + 0.5) * 2^-24;  r = sqrt(-2 ln u_a);  even element r cos(2 pi u_b), odd element r sin(2 pi u_b)
+ *   with (a, b) = (w0, w1) and (w2, w3).  u >= 2^-25, so |eps| <= sqrt(50 ln 2) = 5.89: the normal tail beyond is cut
+ *   (probability 4e-9 per element).
+ * gw_sdl_forward: out = x + (alpha[c] * style[r]) * e with e = noise[i] if noise is given, else eps(key, i) (x NULL with
+ * alpha and style NULL: out = e, the raw noise).  gw_sdl_backward (the gradient of x is dy itself): with
+ * R[r] = sum_s dy[r, s] * e, d_style[r] = alpha[c] * R[r] and d_alpha[c] = sum_b style[b, c] * R[b, c] (either may be NULL);
+ * e is regenerated from the key, nothing of the size of x is kept.
+ * gw_film_forward: out = x * gamma[r] + beta[r].  gw_film_backward: dx = dy * gamma[r] (needs gamma), d_gamma[r] =
+ * sum_s dy * x (needs x), d_beta[r] = sum_s dy; each output may be NULL.
+ * Both backwards take gw_modulate_workspace_bytes(rows, spatial) bytes of scratch (a host-side query). */
+size_t gw_modulate_workspace_bytes(int64_t rows, int64_t spatial);
+int gw_sdl_forward(int64_t rows, int32_t channels, int64_t spatial, const float* x, const float* style, const float* alpha,
+                   const uint32_t* key, const float* noise, float* out, void* stream);
+int gw_sdl_backward(int64_t rows, int32_t channels, int64_t spatial, const float* dy, const float* style, const float* alpha,
+                    const uint32_t* key, const float* noise, void* workspace, size_t workspace_bytes, float* d_style,
+                    float* d_alpha, void* stream);
+int gw_film_forward(int64_t rows, int64_t spatial, const float* x, const float* gamma, const float* beta, float* out, void* stream);
+int gw_film_backward(int64_t rows, int64_t spatial, const float* dy, const float* x, const float* gamma, void* workspace,
+                     size_t workspace_bytes, float* dx, float* d_gamma, float* d_beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
