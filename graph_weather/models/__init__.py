@@ -6,8 +6,12 @@ from graph_weather_amd import (  # noqa: F401
     Encoder,
     GraphCast,
     GraphCastConfig,
+    ImageMetaModel,
+    MetaModel,
     Processor,
     RegionalForecaster,
     RegionalForecasterConfig,
     StochasticDecompositionLayer,
+    WrapperImageModel,
+    WrapperMetaModel,
 )

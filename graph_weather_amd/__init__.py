@@ -31,6 +31,7 @@ from .regional import (  # noqa: F401
 from .constraint import PhysicalConstraintLayer  # noqa: F401  (csrc/gw_constraint.hip)
 from .thermalizer import AdaptiveUNet, ThermalizerLayer  # noqa: F401  (csrc/gw_thermal.hip)
 from .modulation import FiLMApplier, FiLMGenerator, StochasticDecompositionLayer  # noqa: F401  (csrc/gw_modulate.hip)
+from .fengwu_ghr import ImageMetaModel, MetaModel, WrapperImageModel, WrapperMetaModel  # noqa: F401  (csrc/gw_fengwu.hip)
 from .graphed import ForwardGraph  # noqa: F401  (the inference forward as one HIP graph)
 from .rollout import rollout  # noqa: F401
 from .optim import AdamW  # noqa: F401

@@ -36,6 +36,8 @@ EXPORTS = [
     "gw_amse_mmax", "gw_amse_dft_rows", "gw_amse_legendre_floats", "gw_amse_coeff_floats", "gw_amse_workspace_bytes",
     "gw_amse_forward", "gw_amse_backward",
     "gw_modulate_workspace_bytes", "gw_sdl_forward", "gw_sdl_backward", "gw_film_forward", "gw_film_backward",
+    "gw_attention_forward", "gw_attention_backward", "gw_knn_interpolate_forward", "gw_knn_interpolate_backward",
+    "gw_gelu_forward", "gw_gelu_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -313,6 +315,22 @@ def lib():
     L.gw_film_backward.restype = c_int
     L.gw_film_backward.argtypes = [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                    c_void_p]
+    L.gw_attention_forward.restype = c_int
+    L.gw_attention_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_void_p,
+                                       c_int32, c_void_p, c_void_p]
+    L.gw_attention_backward.restype = c_int
+    L.gw_attention_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_void_p,
+                                        c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]
+    L.gw_knn_interpolate_forward.restype = c_int
+    L.gw_knn_interpolate_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                             c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p]
+    L.gw_knn_interpolate_backward.restype = c_int
+    L.gw_knn_interpolate_backward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                              c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p]
+    L.gw_gelu_forward.restype = c_int
+    L.gw_gelu_forward.argtypes = [c_int64, c_void_p, c_void_p, c_void_p]
+    L.gw_gelu_backward.restype = c_int
+    L.gw_gelu_backward.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

@@ -647,6 +647,41 @@ int gw_film_forward(int64_t rows, int64_t spatial, const float* x, const float* 
 int gw_film_backward(int64_t rows, int64_t spatial, const float* dy, const float* x, const float* gamma, void* workspace,
                      size_t workspace_bytes, float* dx, float* d_gamma, float* d_beta, void* stream);
 
+/* =====================================================================================================================
+ * FengWu-GHR (graph_weather/models/fengwu_ghr/layers.py), csrc/gw_fengwu.hip: softmax attention, knn_interpolate and the
+ * exact GELU.  fp32 only; no atomics, no host synchronisation, every sum in one fixed order (bitwise reproducible).
+ *
+ * Attention: out[b, i, h, :] = sum_j softmax_j(scale * q[b, i, h, :] . k[b, j, h, :]) v[b, j, h, :] for `batch` x `heads`
+ * independent pairs of `n` rows and `dim_head` <= 128 features (GW_E_UNSUPPORTED above).  q, k, v are read in place: row
+ * (b, i) of head h starts at x + (b * n + i) * ld_qkv + h * dim_head - three column blocks of the [batch * n, 3 * heads *
+ * dim_head] output of to_qkv, for instance.  out [batch * n, heads * dim_head] (leading dimension ld_out) is in the
+ * "b n (h d)" order; lse [2, batch * heads, n] receives the log-sum-exp of every score row in two parts whose sum it is:
+ * plane 0 the row maximum m of the scaled scores, plane 1 log sum_j exp(s_j - m) (kept apart because one fp32 of the sum
+ * would carry 4e-6 of rounding into every recomputed probability at scores of 100).  The n x n scores are never written
+ * (online softmax); n <= 16 runs one pair per wave, four per workgroup.
+ * gw_attention_backward recomputes the probabilities from q, k and lse: delta [batch * heads, n] (scratch the caller
+ * provides) = rowsum(dout * out), then one launch over key blocks writes dk and dv and one over query blocks dq, all laid
+ * out like q, k, v with leading dimension ld_dqkv. */
+int gw_attention_forward(int32_t batch, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k, const float* v,
+                         int32_t ld_qkv, float scale, float* out, int32_t ld_out, float* lse, void* stream);
+int gw_attention_backward(int32_t batch, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k, const float* v,
+                          int32_t ld_qkv, float scale, const float* out, int32_t ld_out, const float* dout, int32_t ld_dout,
+                          const float* lse, float* delta, float* dq, float* dk, float* dv, int32_t ld_dqkv, void* stream);
+/* knn_interpolate: y[b, t, c] = sum_j w[t, j] * x[b, idx[t, j], c] / sum_j w[t, j] over the k neighbours of target t
+ * (idx, w: [n_tgt, k], built on the host).  Element (b, row, c) of x / y lies at b * stride_b + row * stride_row + c *
+ * stride_c floats, so [B, n, c] rows and [B, c, h, w] images are used as they lie.  The backward walks the CSR of the
+ * transposed assignment: source s owns entries src_ptr[s] .. src_ptr[s + 1] - 1, entry e pointing at target src_tgt[e] with
+ * weight src_w[e] = w / (sum of that target's weights); dx[b, s, c] = sum_e src_w[e] * dy[b, src_tgt[e], c]. */
+int gw_knn_interpolate_forward(int32_t batch, int32_t n_tgt, int32_t channels, int32_t k, const int32_t* idx, const float* w,
+                               const float* x, int64_t x_stride_b, int64_t x_stride_row, int64_t x_stride_c, float* y,
+                               int64_t y_stride_b, int64_t y_stride_row, int64_t y_stride_c, void* stream);
+int gw_knn_interpolate_backward(int32_t batch, int32_t n_src, int32_t channels, const int32_t* src_ptr, const int32_t* src_tgt,
+                                const float* src_w, const float* dy, int64_t y_stride_b, int64_t y_stride_row, int64_t y_stride_c,
+                                float* dx, int64_t x_stride_b, int64_t x_stride_row, int64_t x_stride_c, void* stream);
+/* y = x * Phi(x) with the exact (erf) normal CDF, on n dense floats; dx = dy * (Phi(x) + x * phi(x)). */
+int gw_gelu_forward(int64_t n, const float* x, float* y, void* stream);
+int gw_gelu_backward(int64_t n, const float* x, const float* dy, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
