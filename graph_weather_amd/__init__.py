@@ -32,6 +32,15 @@ from .constraint import PhysicalConstraintLayer  # noqa: F401  (csrc/gw_constrai
 from .thermalizer import AdaptiveUNet, ThermalizerLayer  # noqa: F401  (csrc/gw_thermal.hip)
 from .modulation import FiLMApplier, FiLMGenerator, StochasticDecompositionLayer  # noqa: F401  (csrc/gw_modulate.hip)
 from .fengwu_ghr import ImageMetaModel, MetaModel, WrapperImageModel, WrapperMetaModel  # noqa: F401  (csrc/gw_fengwu.hip)
+from .cafa import (  # noqa: F401  (csrc/gw_cafa.hip, axial addressing of csrc/gw_fengwu.hip)
+    AxialAttention,
+    CaFADecoder,
+    CaFAEncoder,
+    CaFAForecaster,
+    CaFAProcessor,
+    FactorizedAttention,
+    FactorizedTransformerBlock,
+)
 from .graphed import ForwardGraph  # noqa: F401  (the inference forward as one HIP graph)
 from .rollout import rollout  # noqa: F401
 from .optim import AdamW  # noqa: F401

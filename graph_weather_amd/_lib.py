@@ -38,6 +38,9 @@ EXPORTS = [
     "gw_modulate_workspace_bytes", "gw_sdl_forward", "gw_sdl_backward", "gw_film_forward", "gw_film_backward",
     "gw_attention_forward", "gw_attention_backward", "gw_knn_interpolate_forward", "gw_knn_interpolate_backward",
     "gw_gelu_forward", "gw_gelu_backward",
+    "gw_attention_axial_forward", "gw_attention_axial_backward",
+    "gw_patch_workspace_bytes", "gw_patch_embed_forward", "gw_patch_embed_backward", "gw_patch_expand_forward",
+    "gw_patch_expand_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -331,6 +334,25 @@ def lib():
     L.gw_gelu_forward.argtypes = [c_int64, c_void_p, c_void_p, c_void_p]
     L.gw_gelu_backward.restype = c_int
     L.gw_gelu_backward.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_attention_axial_forward.restype = c_int
+    L.gw_attention_axial_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
+                                             c_float, c_void_p, POINTER(c_int64), c_void_p, c_void_p]
+    L.gw_attention_axial_backward.restype = c_int
+    L.gw_attention_axial_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
+                                              c_float, c_void_p, POINTER(c_int64), c_void_p, POINTER(c_int64), c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]
+    L.gw_patch_workspace_bytes.restype = c_size_t
+    L.gw_patch_workspace_bytes.argtypes = [c_int32] * 6
+    L.gw_patch_embed_forward.restype = c_int
+    L.gw_patch_embed_forward.argtypes = [c_int32] * 6 + [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]
+    L.gw_patch_embed_backward.restype = c_int
+    L.gw_patch_embed_backward.argtypes = [c_int32] * 6 + [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_void_p,
+                                                          c_void_p, c_void_p]
+    L.gw_patch_expand_forward.restype = c_int
+    L.gw_patch_expand_forward.argtypes = [c_int32] * 6 + [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_patch_expand_backward.restype = c_int
+    L.gw_patch_expand_backward.argtypes = [c_int32] * 6 + [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int32,
+                                                           c_void_p, c_void_p, c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

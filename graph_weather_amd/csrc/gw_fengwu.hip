@@ -9,6 +9,10 @@
 //   gw_attention_backward   recomputes P from Q, K and the log-sum-exp; delta = rowsum(dO o O) by a prologue, then one launch over
 //                           key blocks (dK, dV resident across the query sweep) and one over query blocks (dQ): no atomics, no
 //                           hand-off between workgroups, bitwise reproducible
+//   gw_attention_axial_forward / _backward   the same kernels on sequences that lie along one axis of a token grid (CaFA,
+//                           graph_weather/models/cafa/factorize.py): a sequence is (outer o, inner s) and its token i starts at
+//                           x + o st[0] + s st[1] + i st[2] (64-bit strides), so attention along the height of [B, H, W, 3 inner]
+//                           rows needs no transposing copy; the two entry points above are inner = 1, st = (n ld, 0, ld)
 //   gw_knn_interpolate_forward / _backward   inverse-squared-distance interpolation over k = 4 neighbours through strides
 //   gw_gelu_forward / _backward              exact (erf) GELU
 //
@@ -48,18 +52,21 @@ int failf(int code, const char* msg) { return set_error(code, msg); }
 struct AttnArgs {
   int batch, heads, n, d;
   int64_t pairs;
+  int inner;  // batch = outer * inner sequences; pair = ((o, s), h) with s the fast sequence index
   const float *q, *k, *v;
-  int ld;  // row (b, i) of pair (b, h) starts at x + (b n + i) ld + h d
+  // token i of head h of sequence (o, s) starts at x + o st[0] + s st[1] + i st[2] + h d (strides in floats); the plain
+  // [batch n, ld] rows are inner = 1, st = (n ld, 0, ld)
+  int64_t sq[3];  // q, k, v
   float scale;
   float* out;  // forward: written; backward: the forward's output
-  int ld_out;
+  int64_t so[3];
   float* lse;  // [2, pairs, n]: the row maximum m of the scaled scores, then log sum exp(s - m) - the log-sum-exp in two parts
   const float* dout;
-  int ld_dout;
+  int64_t sg[3];
   float* delta;  // [pairs, n]
   float *dq, *dk, *dv;
-  int ld_dqkv;
-  int vec;  // every pointer 16-byte aligned, every leading dimension and dim_head a multiple of 4
+  int64_t sd[3];  // dq, dk, dv
+  int vec;  // every pointer 16-byte aligned, every stride and dim_head a multiple of 4
 };
 
 template <int DP>
@@ -95,11 +102,11 @@ __device__ __forceinline__ void store4(float* row, int d0, int D, bool vec, f32x
 
 // rows r0 .. r0 + ROWS - 1 of one pair (base = its row 0, or NULL) into an LDS tile, zero filled past n and past D
 template <int DP, int ROWS>
-__device__ __forceinline__ void stage_rows(float* lds, const float* base, int ld, int r0, int n, int D, bool vec, int tid, int nthreads) {
+__device__ __forceinline__ void stage_rows(float* lds, const float* base, int64_t ld, int r0, int n, int D, bool vec, int tid, int nthreads) {
   constexpr int C4 = DP / 4, LD = Cfg<DP>::LD;
   for (int idx = tid; idx < ROWS * C4; idx += nthreads) {
     const int row = idx / C4, c4 = idx - row * C4;
-    const float* rp = (base != nullptr && r0 + row < n) ? base + (size_t)(r0 + row) * ld : nullptr;
+    const float* rp = (base != nullptr && r0 + row < n) ? base + (int64_t)(r0 + row) * ld : nullptr;
     *(f32x4*)(lds + row * LD + 4 * c4) = load4(rp, 4 * c4, D, vec);
   }
 }
@@ -162,8 +169,10 @@ struct Place {
   int64_t pair;
   int row0;
   bool ok;        // the pair exists
-  size_t base;    // offset of row 0 of the pair in a [rows, ld] operand, in rows (b n); the head offset h d is added by the caller
+  int o, s;       // its sequence
   int h;
+  // offset in floats of token 0 of the sequence in an operand with strides st; the head offset h d is added by the caller
+  __device__ __forceinline__ int64_t at(const int64_t (&st)[3]) const { return o * st[0] + s * st[1]; }
 };
 template <bool PACKED, int PW>
 __device__ __forceinline__ Place place_of(const AttnArgs& a, int wave) {
@@ -180,7 +189,8 @@ __device__ __forceinline__ Place place_of(const AttnArgs& a, int wave) {
   const int64_t pr = p.ok ? p.pair : 0;
   const int64_t b = pr / a.heads;
   p.h = (int)(pr - b * a.heads);
-  p.base = (size_t)b * a.n;
+  p.o = (int)(b / a.inner);
+  p.s = (int)(b - (int64_t)p.o * a.inner);
   return p;
 }
 
@@ -198,7 +208,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs a) {
   const size_t col = (size_t)pl.h * D;
   const int qrow = pl.row0 + i;
   const bool qok = pl.ok && qrow < n;
-  const float* qp = qok ? a.q + (pl.base + qrow) * a.ld + col : nullptr;
+  const int64_t bq = pl.at(a.sq), tq = a.sq[2];
+  const float* qp = qok ? a.q + bq + qrow * tq + col : nullptr;
   f32x4 qf[NC], o[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -206,18 +217,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs a) {
     o[c] = zero4();
   }
   float m = -INFINITY, l = 0.f;
-  const float* kbase = pl.ok ? a.k + pl.base * a.ld + col : nullptr;
-  const float* vbase = pl.ok ? a.v + pl.base * a.ld + col : nullptr;
+  const float* kbase = pl.ok ? a.k + bq + col : nullptr;
+  const float* vbase = pl.ok ? a.v + bq + col : nullptr;
   float* ks = PACKED ? Ks + wave * 16 * LD : Ks;
   float* vs = PACKED ? Vs + wave * 16 * LD : Vs;
   for (int k0 = 0; k0 < n; k0 += TB) {
     __syncthreads();
     if (PACKED) {
-      stage_rows<DP, 16>(ks, kbase, a.ld, k0, n, D, vec, lane, 64);
-      stage_rows<DP, 16>(vs, vbase, a.ld, k0, n, D, vec, lane, 64);
+      stage_rows<DP, 16>(ks, kbase, tq, k0, n, D, vec, lane, 64);
+      stage_rows<DP, 16>(vs, vbase, tq, k0, n, D, vec, lane, 64);
     } else {
-      stage_rows<DP, TB>(ks, kbase, a.ld, k0, n, D, vec, threadIdx.x, 256);
-      stage_rows<DP, TB>(vs, vbase, a.ld, k0, n, D, vec, threadIdx.x, 256);
+      stage_rows<DP, TB>(ks, kbase, tq, k0, n, D, vec, threadIdx.x, 256);
+      stage_rows<DP, TB>(vs, vbase, tq, k0, n, D, vec, threadIdx.x, 256);
     }
     __syncthreads();
     f32x4 s[NT];
@@ -254,7 +265,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs a) {
   l = group_sum(l);
   if (qok) {
     const float inv = 1.0f / l;
-    float* op = a.out + (pl.base + qrow) * a.ld_out + col;
+    float* op = a.out + pl.at(a.so) + qrow * a.so[2] + col;
 #pragma unroll
     for (int c = 0; c < NC; ++c) store4(op, 16 * c + 4 * kq, D, vec, o[c] * inv);
     if (kq == 0) {
@@ -272,9 +283,9 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const AttnArgs a) {
     const int i = (int)(t - pair * a.n);
     const int64_t b = pair / a.heads;
     const int h = (int)(pair - b * a.heads);
-    const size_t row = (size_t)b * a.n + i;
-    const float* op = a.out + row * a.ld_out + (size_t)h * a.d;
-    const float* gp = a.dout + row * a.ld_dout + (size_t)h * a.d;
+    const int64_t o = b / a.inner, sq = b - o * a.inner;
+    const float* op = a.out + o * a.so[0] + sq * a.so[1] + i * a.so[2] + (size_t)h * a.d;
+    const float* gp = a.dout + o * a.sg[0] + sq * a.sg[1] + i * a.sg[2] + (size_t)h * a.d;
     // one fmaf chain in the order the MFMAs of dP = dO . V^T walk the features (chunk c, K-step ks, lane group kq: d = 16 c + 4 kq +
     // ks): delta and dP then round alike, and with a single key (O = V, p = 1) dS = p (dP - delta) is exactly zero
     // (an fp32-input MFMA accumulates as a k-ordered fmaf chain; should that ever change, the single-key case shows one rounding
@@ -304,8 +315,9 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs a) {
   const size_t col = (size_t)pl.h * D;
   const int qrow = pl.row0 + i;
   const bool qok = pl.ok && qrow < n;
-  const float* qp = qok ? a.q + (pl.base + qrow) * a.ld + col : nullptr;
-  const float* gp = qok ? a.dout + (pl.base + qrow) * a.ld_dout + col : nullptr;
+  const int64_t bq = pl.at(a.sq), tq = a.sq[2];
+  const float* qp = qok ? a.q + bq + qrow * tq + col : nullptr;
+  const float* gp = qok ? a.dout + pl.at(a.sg) + qrow * a.sg[2] + col : nullptr;
   f32x4 qf[NC], gf[NC], dq[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -317,18 +329,18 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs a) {
   const float mrow = qok ? ldg1(a.lse + (size_t)pl.pair * n + qrow) : INFINITY;
   const float lrow = qok ? ldg1(a.lse + (size_t)(a.pairs + pl.pair) * n + qrow) : 0.f;
   const float delta = qok ? ldg1(a.delta + (size_t)pl.pair * n + qrow) : 0.f;
-  const float* kbase = pl.ok ? a.k + pl.base * a.ld + col : nullptr;
-  const float* vbase = pl.ok ? a.v + pl.base * a.ld + col : nullptr;
+  const float* kbase = pl.ok ? a.k + bq + col : nullptr;
+  const float* vbase = pl.ok ? a.v + bq + col : nullptr;
   float* ks = PACKED ? Ks + wave * 16 * LD : Ks;
   float* vs = PACKED ? Vs + wave * 16 * LD : Vs;
   for (int k0 = 0; k0 < n; k0 += TB) {
     __syncthreads();
     if (PACKED) {
-      stage_rows<DP, 16>(ks, kbase, a.ld, k0, n, D, vec, lane, 64);
-      stage_rows<DP, 16>(vs, vbase, a.ld, k0, n, D, vec, lane, 64);
+      stage_rows<DP, 16>(ks, kbase, tq, k0, n, D, vec, lane, 64);
+      stage_rows<DP, 16>(vs, vbase, tq, k0, n, D, vec, lane, 64);
     } else {
-      stage_rows<DP, TB>(ks, kbase, a.ld, k0, n, D, vec, threadIdx.x, 256);
-      stage_rows<DP, TB>(vs, vbase, a.ld, k0, n, D, vec, threadIdx.x, 256);
+      stage_rows<DP, TB>(ks, kbase, tq, k0, n, D, vec, threadIdx.x, 256);
+      stage_rows<DP, TB>(vs, vbase, tq, k0, n, D, vec, threadIdx.x, 256);
     }
     __syncthreads();
     f32x4 s[NT], dp[NT];
@@ -351,7 +363,7 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs a) {
     prod_acc<DP, NT>(dq, ks, s, i, kq);
   }
   if (qok) {
-    float* op = a.dq + (pl.base + qrow) * a.ld_dqkv + col;
+    float* op = a.dq + pl.at(a.sd) + qrow * a.sd[2] + col;
 #pragma unroll
     for (int c = 0; c < NC; ++c) store4(op, 16 * c + 4 * kq, D, vec, dq[c]);
   }
@@ -374,8 +386,9 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) {
   const size_t col = (size_t)pl.h * D;
   const int krow = pl.row0 + i;
   const bool kok = pl.ok && krow < n;
-  const float* kp = kok ? a.k + (pl.base + krow) * a.ld + col : nullptr;
-  const float* vp = kok ? a.v + (pl.base + krow) * a.ld + col : nullptr;
+  const int64_t bq = pl.at(a.sq), tq = a.sq[2], tg = a.sg[2];
+  const float* kp = kok ? a.k + bq + krow * tq + col : nullptr;
+  const float* vp = kok ? a.v + bq + krow * tq + col : nullptr;
   f32x4 kf[NC], vf[NC], dk[NC], dv[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -384,8 +397,8 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) {
     dk[c] = zero4();
     dv[c] = zero4();
   }
-  const float* qbase = pl.ok ? a.q + pl.base * a.ld + col : nullptr;
-  const float* gbase = pl.ok ? a.dout + pl.base * a.ld_dout + col : nullptr;
+  const float* qbase = pl.ok ? a.q + bq + col : nullptr;
+  const float* gbase = pl.ok ? a.dout + pl.at(a.sg) + col : nullptr;
   const int off = PACKED ? wave * 16 : 0;
   float* qs = Qs + off * LD;
   float* gs = Gs + off * LD;
@@ -395,8 +408,8 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) {
   for (int q0 = 0; q0 < n; q0 += TB) {
     __syncthreads();
     if (PACKED) {
-      stage_rows<DP, 16>(qs, qbase, a.ld, q0, n, D, vec, lane, 64);
-      stage_rows<DP, 16>(gs, gbase, a.ld_dout, q0, n, D, vec, lane, 64);
+      stage_rows<DP, 16>(qs, qbase, tq, q0, n, D, vec, lane, 64);
+      stage_rows<DP, 16>(gs, gbase, tg, q0, n, D, vec, lane, 64);
       if (lane < 16) {
         const bool ok = pl.ok && q0 + lane < n;
         ms[lane] = ok ? ldg1(a.lse + (size_t)pl.pair * n + q0 + lane) : INFINITY;  // rows past the end: p = 0
@@ -404,8 +417,8 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) {
         ds[lane] = ok ? ldg1(a.delta + (size_t)pl.pair * n + q0 + lane) : 0.f;
       }
     } else {
-      stage_rows<DP, TB>(qs, qbase, a.ld, q0, n, D, vec, threadIdx.x, 256);
-      stage_rows<DP, TB>(gs, gbase, a.ld_dout, q0, n, D, vec, threadIdx.x, 256);
+      stage_rows<DP, TB>(qs, qbase, tq, q0, n, D, vec, threadIdx.x, 256);
+      stage_rows<DP, TB>(gs, gbase, tg, q0, n, D, vec, threadIdx.x, 256);
       if ((int)threadIdx.x < TB) {
         const bool ok = pl.ok && q0 + (int)threadIdx.x < n;
         ms[threadIdx.x] = ok ? ldg1(a.lse + (size_t)pl.pair * n + q0 + threadIdx.x) : INFINITY;
@@ -439,8 +452,9 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) {
     prod_acc<DP, NT>(dk, qs, dp, i, kq);
   }
   if (kok) {
-    float* okp = a.dk + (pl.base + krow) * a.ld_dqkv + col;
-    float* ovp = a.dv + (pl.base + krow) * a.ld_dqkv + col;
+    const int64_t bd = pl.at(a.sd) + krow * a.sd[2] + col;
+    float* okp = a.dk + bd;
+    float* ovp = a.dv + bd;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       store4(okp, 16 * c + 4 * kq, D, vec, dk[c]);
@@ -558,23 +572,31 @@ unsigned stream_blocks(int64_t n) {
   return (unsigned)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
 }
 
-}  // namespace
+void set3(int64_t (&st)[3], const int64_t* from) { st[0] = from[0], st[1] = from[1], st[2] = from[2]; }
+void rows3(int64_t (&st)[3], int32_t n, int32_t ld) { st[0] = (int64_t)n * ld, st[1] = 0, st[2] = ld; }
+bool mult4(const int64_t (&st)[3]) { return st[0] % 4 == 0 && st[1] % 4 == 0 && st[2] % 4 == 0; }
 
-extern "C" {
+// sizes of the axial entry points (the strides are the caller's statement of where the sequences lie)
+int axial_args(AttnArgs& a, const char* what, int32_t outer, int32_t inner, int32_t heads, int32_t n, int32_t d) {
+  static char msg[160];
+  if (outer <= 0 || inner <= 0 || heads <= 0 || n <= 0 || d <= 0 || d > 128) {
+    snprintf(msg, sizeof msg, "%s: bad arguments", what);
+    return failf(GW_E_BADARG, msg);
+  }
+  const int64_t seqs = (int64_t)outer * inner;
+  if (seqs * n >= ((int64_t)1 << 31) || seqs * heads >= ((int64_t)1 << 31)) {
+    snprintf(msg, sizeof msg, "%s: row count exceeds int32", what);
+    return failf(GW_E_UNSUPPORTED, msg);
+  }
+  a.batch = (int)seqs, a.inner = inner, a.heads = heads, a.n = n, a.d = d, a.pairs = seqs * heads;
+  return GW_OK;
+}
 
-int gw_attention_forward(int32_t batch, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k, const float* v,
-                         int32_t ld_qkv, float scale, float* out, int32_t ld_out, float* lse, void* stream) {
-  if (!q || !k || !v || !out || !lse) return failf(GW_E_BADARG, "gw_attention_forward: bad arguments");
-  int rc = attn_check("gw_attention_forward", batch, heads, n, dim_head, (int64_t)heads * dim_head, ld_qkv);
-  if (rc != GW_OK) return rc;
-  if (ld_out < heads * dim_head) return failf(GW_E_BADARG, "gw_attention_forward: bad arguments");
-  AttnArgs a = {};
-  a.batch = batch, a.heads = heads, a.n = n, a.d = dim_head, a.pairs = (int64_t)batch * heads;
-  a.q = q, a.k = k, a.v = v, a.ld = ld_qkv, a.scale = scale, a.out = out, a.ld_out = ld_out, a.lse = lse;
-  a.vec = dim_head % 4 == 0 && ld_qkv % 4 == 0 && ld_out % 4 == 0 && al16(q) && al16(k) && al16(v) && al16(out);
-  const bool packed = n <= 16;
+int attn_forward_launch(AttnArgs& a, void* stream) {
+  a.vec = a.d % 4 == 0 && mult4(a.sq) && mult4(a.so) && al16(a.q) && al16(a.k) && al16(a.v) && al16(a.out);
+  const bool packed = a.n <= 16;
   const dim3 grid(attn_grid(a, packed));
-  by_dim_head(dim_head, [&](auto dp) {
+  by_dim_head(a.d, [&](auto dp) {
     constexpr int DP = decltype(dp)::value;
     if (packed)
       hipLaunchKernelGGL((attn_fwd_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
@@ -583,6 +605,73 @@ int gw_attention_forward(int32_t batch, int32_t heads, int32_t n, int32_t dim_he
     return 0;
   });
   return check_launch("attn_fwd_kernel launch");
+}
+
+int attn_backward_launch(AttnArgs& a, void* stream) {
+  a.vec = a.d % 4 == 0 && mult4(a.sq) && mult4(a.sg) && mult4(a.sd) && al16(a.q) && al16(a.k) && al16(a.v) && al16(a.dout) &&
+          al16(a.dq) && al16(a.dk) && al16(a.dv);
+  hipLaunchKernelGGL(attn_delta_kernel, dim3(stream_blocks(a.pairs * a.n)), dim3(256), 0, (hipStream_t)stream, a);
+  int rc = check_launch("attn_delta_kernel launch");
+  if (rc != GW_OK) return rc;
+  const bool packed = a.n <= 16;
+  const dim3 grid(attn_grid(a, packed));
+  by_dim_head(a.d, [&](auto dp) {
+    constexpr int DP = decltype(dp)::value;
+    if (packed) {
+      hipLaunchKernelGGL((attn_dkv_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
+      hipLaunchKernelGGL((attn_dq_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
+    } else {
+      hipLaunchKernelGGL((attn_dkv_kernel<DP, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+      hipLaunchKernelGGL((attn_dq_kernel<DP, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    }
+    return 0;
+  });
+  return check_launch("attn_dkv_kernel / attn_dq_kernel launch");
+}
+
+}  // namespace
+
+extern "C" {
+
+int gw_attention_axial_forward(int32_t outer, int32_t inner, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k,
+                               const float* v, const int64_t* stride_qkv, float scale, float* out, const int64_t* stride_out, float* lse,
+                               void* stream) {
+  if (!q || !k || !v || !out || !lse || !stride_qkv || !stride_out) return failf(GW_E_BADARG, "gw_attention_axial_forward: bad arguments");
+  AttnArgs a = {};
+  int rc = axial_args(a, "gw_attention_axial_forward", outer, inner, heads, n, dim_head);
+  if (rc != GW_OK) return rc;
+  a.q = q, a.k = k, a.v = v, a.scale = scale, a.out = out, a.lse = lse;
+  set3(a.sq, stride_qkv), set3(a.so, stride_out);
+  return attn_forward_launch(a, stream);
+}
+
+int gw_attention_axial_backward(int32_t outer, int32_t inner, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k,
+                                const float* v, const int64_t* stride_qkv, float scale, const float* out, const int64_t* stride_out,
+                                const float* dout, const int64_t* stride_dout, const float* lse, float* delta, float* dq, float* dk,
+                                float* dv, const int64_t* stride_dqkv, void* stream) {
+  if (!q || !k || !v || !out || !dout || !lse || !delta || !dq || !dk || !dv || !stride_qkv || !stride_out || !stride_dout || !stride_dqkv)
+    return failf(GW_E_BADARG, "gw_attention_axial_backward: bad arguments");
+  AttnArgs a = {};
+  int rc = axial_args(a, "gw_attention_axial_backward", outer, inner, heads, n, dim_head);
+  if (rc != GW_OK) return rc;
+  a.q = q, a.k = k, a.v = v, a.scale = scale, a.out = const_cast<float*>(out), a.lse = const_cast<float*>(lse);
+  a.dout = dout, a.delta = delta, a.dq = dq, a.dk = dk, a.dv = dv;
+  set3(a.sq, stride_qkv), set3(a.so, stride_out), set3(a.sg, stride_dout), set3(a.sd, stride_dqkv);
+  return attn_backward_launch(a, stream);
+}
+
+// the plain [batch n, ld] rows: one sequence per outer index
+int gw_attention_forward(int32_t batch, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k, const float* v,
+                         int32_t ld_qkv, float scale, float* out, int32_t ld_out, float* lse, void* stream) {
+  if (!q || !k || !v || !out || !lse) return failf(GW_E_BADARG, "gw_attention_forward: bad arguments");
+  int rc = attn_check("gw_attention_forward", batch, heads, n, dim_head, (int64_t)heads * dim_head, ld_qkv);
+  if (rc != GW_OK) return rc;
+  if (ld_out < heads * dim_head) return failf(GW_E_BADARG, "gw_attention_forward: bad arguments");
+  AttnArgs a = {};
+  a.batch = batch, a.inner = 1, a.heads = heads, a.n = n, a.d = dim_head, a.pairs = (int64_t)batch * heads;
+  a.q = q, a.k = k, a.v = v, a.scale = scale, a.out = out, a.lse = lse;
+  rows3(a.sq, n, ld_qkv), rows3(a.so, n, ld_out);
+  return attn_forward_launch(a, stream);
 }
 
 int gw_attention_backward(int32_t batch, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k, const float* v,
@@ -595,29 +684,11 @@ int gw_attention_backward(int32_t batch, int32_t heads, int32_t n, int32_t dim_h
   const int inner = heads * dim_head;
   if (ld_out < inner || ld_dout < inner || ld_dqkv < inner) return failf(GW_E_BADARG, "gw_attention_backward: bad arguments");
   AttnArgs a = {};
-  a.batch = batch, a.heads = heads, a.n = n, a.d = dim_head, a.pairs = (int64_t)batch * heads;
-  a.q = q, a.k = k, a.v = v, a.ld = ld_qkv, a.scale = scale, a.out = const_cast<float*>(out), a.ld_out = ld_out;
-  a.lse = const_cast<float*>(lse), a.dout = dout, a.ld_dout = ld_dout, a.delta = delta;
-  a.dq = dq, a.dk = dk, a.dv = dv, a.ld_dqkv = ld_dqkv;
-  a.vec = dim_head % 4 == 0 && ld_qkv % 4 == 0 && ld_dout % 4 == 0 && ld_dqkv % 4 == 0 && al16(q) && al16(k) && al16(v) &&
-          al16(dout) && al16(dq) && al16(dk) && al16(dv);
-  hipLaunchKernelGGL(attn_delta_kernel, dim3(stream_blocks(a.pairs * n)), dim3(256), 0, (hipStream_t)stream, a);
-  rc = check_launch("attn_delta_kernel launch");
-  if (rc != GW_OK) return rc;
-  const bool packed = n <= 16;
-  const dim3 grid(attn_grid(a, packed));
-  by_dim_head(dim_head, [&](auto dp) {
-    constexpr int DP = decltype(dp)::value;
-    if (packed) {
-      hipLaunchKernelGGL((attn_dkv_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
-      hipLaunchKernelGGL((attn_dq_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
-    } else {
-      hipLaunchKernelGGL((attn_dkv_kernel<DP, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
-      hipLaunchKernelGGL((attn_dq_kernel<DP, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
-    }
-    return 0;
-  });
-  return check_launch("attn_dkv_kernel / attn_dq_kernel launch");
+  a.batch = batch, a.inner = 1, a.heads = heads, a.n = n, a.d = dim_head, a.pairs = (int64_t)batch * heads;
+  a.q = q, a.k = k, a.v = v, a.scale = scale, a.out = const_cast<float*>(out), a.lse = const_cast<float*>(lse);
+  a.dout = dout, a.delta = delta, a.dq = dq, a.dk = dk, a.dv = dv;
+  rows3(a.sq, n, ld_qkv), rows3(a.so, n, ld_out), rows3(a.sg, n, ld_dout), rows3(a.sd, n, ld_dqkv);
+  return attn_backward_launch(a, stream);
 }
 
 int gw_knn_interpolate_forward(int32_t batch, int32_t n_tgt, int32_t channels, int32_t k, const int32_t* idx, const float* w,

@@ -667,6 +667,20 @@ int gw_attention_forward(int32_t batch, int32_t heads, int32_t n, int32_t dim_he
 int gw_attention_backward(int32_t batch, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k, const float* v,
                           int32_t ld_qkv, float scale, const float* out, int32_t ld_out, const float* dout, int32_t ld_dout,
                           const float* lse, float* delta, float* dq, float* dk, float* dv, int32_t ld_dqkv, void* stream);
+/* The same kernels on sequences that lie along one axis of a grid (CaFA's axial attention, graph_weather/models/cafa/
+ * factorize.py), without a transposing copy: `outer` x `inner` sequences of n tokens; token i of head h of sequence (o, s)
+ * starts at x + o * stride[0] + s * stride[1] + i * stride[2] + h * dim_head (strides in floats, three per operand group:
+ * q / k / v, out, dout, dq / dk / dv).  For a [B, H, W, 3 * heads * dim_head] projection with row stride ld the width axis is
+ * outer = B, inner = H, n = W, stride = (H W ld, W ld, ld) and the height axis outer = B, inner = W, n = H, stride =
+ * (H W ld, ld, W ld).  lse [2, pairs, n] and delta [pairs, n] are dense with pairs = outer * inner * heads ordered (o, s, h).
+ * gw_attention_forward / _backward are the case inner = 1, stride = (n ld, 0, ld).  dim_head > 128 is GW_E_BADARG here. */
+int gw_attention_axial_forward(int32_t outer, int32_t inner, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k,
+                               const float* v, const int64_t* stride_qkv, float scale, float* out, const int64_t* stride_out, float* lse,
+                               void* stream);
+int gw_attention_axial_backward(int32_t outer, int32_t inner, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k,
+                                const float* v, const int64_t* stride_qkv, float scale, const float* out, const int64_t* stride_out,
+                                const float* dout, const int64_t* stride_dout, const float* lse, float* delta, float* dq, float* dk,
+                                float* dv, const int64_t* stride_dqkv, void* stream);
 /* knn_interpolate: y[b, t, c] = sum_j w[t, j] * x[b, idx[t, j], c] / sum_j w[t, j] over the k neighbours of target t
  * (idx, w: [n_tgt, k], built on the host).  Element (b, row, c) of x / y lies at b * stride_b + row * stride_row + c *
  * stride_c floats, so [B, n, c] rows and [B, c, h, w] images are used as they lie.  The backward walks the CSR of the
@@ -681,6 +695,30 @@ int gw_knn_interpolate_backward(int32_t batch, int32_t n_src, int32_t channels, 
 /* y = x * Phi(x) with the exact (erf) normal CDF, on n dense floats; dx = dy * (Phi(x) + x * phi(x)). */
 int gw_gelu_forward(int64_t n, const float* x, float* y, void* stream);
 int gw_gelu_backward(int64_t n, const float* x, const float* dy, float* dx, void* stream);
+
+
+/* =====================================================================================================================
+ * CaFA (graph_weather/models/cafa), csrc/gw_cafa.hip: the patch convolutions as fp32 MFMA products over the patch view of
+ * an NCHW image [batch, channels, h, w] read or written as it lies: oh = ceil(h / f), ow = ceil(w / f) patches per image,
+ * row m = (b, py, px) of the channels-last rows, k = (c, ky, kx) of the weight [dim, channels * f * f] (Conv2d's
+ * [dim, channels, f, f] and ConvTranspose2d's [dim, channels, f, f] alike).  Pixels past h or w read as zero and are never
+ * written.  No atomics, no host synchronisation; the weight and bias gradients are per-slab partials (1024 patches each)
+ * added in slab order, in gw_patch_workspace_bytes (a host-side query; 0 with the error set on bad arguments) of scratch.
+ *   gw_patch_embed_forward    out[m, :dim] = bias + weight . patch(x, m)                              (Conv2d, kernel = stride = f)
+ *   gw_patch_embed_backward   dx (may be NULL), dweight and dbias (both or neither) from dout [rows, dim]
+ *   gw_patch_expand_forward   out[b, c, f py + ky, f px + kx] = bias[c] + sum_d rows[m, d] weight[d, (c, ky, kx)]   (ConvTranspose2d)
+ *   gw_patch_expand_backward  d_rows (may be NULL), dweight and dbias (both or neither) from dout [batch, channels, h, w] */
+size_t gw_patch_workspace_bytes(int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t f, int32_t dim);
+int gw_patch_embed_forward(int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t f, int32_t dim, const float* x,
+                           const float* weight, const float* bias, float* out, int32_t ld_out, void* stream);
+int gw_patch_embed_backward(int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t f, int32_t dim, const float* x,
+                            const float* weight, const float* dout, int32_t ld_dout, void* workspace, size_t workspace_bytes,
+                            float* dx, float* dweight, float* dbias, void* stream);
+int gw_patch_expand_forward(int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t f, int32_t dim, const float* rows,
+                            int32_t ld_rows, const float* weight, const float* bias, float* out, void* stream);
+int gw_patch_expand_backward(int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t f, int32_t dim, const float* rows,
+                             int32_t ld_rows, const float* weight, const float* dout, void* workspace, size_t workspace_bytes,
+                             float* d_rows, int32_t ld_drows, float* dweight, float* dbias, void* stream);
 
 #ifdef __cplusplus
 }
