@@ -144,3 +144,36 @@ def test_isa_of_thermal_kernels(tmp_path):
         assert "v_mfma_f32_16x16x4_f32" in b or "v_mfma_f32_16x16x4f32" in b
     for m in re.finditer(r"\.private_segment_fixed_size:\s+(\d+)", asm):
         assert int(m.group(1)) == 0
+
+
+@pytest.mark.parametrize("B,H,W", [(2, 3, 3), (1, 13, 9), (2, 12, 12)])
+def test_per_operation_oracle_composes_to_score_and_thermalize(B, H, W):
+    """The per-operation row helpers of thermal_oracle.py (what tests/test_gpu_thermal_kernels.py holds each kernel against),
+    composed into simple_net / the UNet and into the diffusion step, are ``score`` and ``thermalize`` (pinned to the reference's
+    fixtures above) to fp64 rounding."""
+    import graph_weather_amd as gw
+
+    F = 6
+    layer = to.fill_(gw.ThermalizerLayer(F), 5)
+    sd = {k: v.double() for k, v in to.strip(layer.state_dict(), "score_model.").items()}
+    g = torch.Generator().manual_seed(100 * B + 10 * H + W)
+    x = torch.randn(B * H * W, F + 2, generator=g, dtype=torch.float64)
+    noise = torch.randn(B * H * W, F, generator=g, dtype=torch.float64)
+    ref = to.score(sd, to.to_image(x, B, H, W))
+    got = to.to_image(to.score_rows(sd, x, B, H, W), B, H, W)
+    assert got.shape == ref.shape
+    assert (got - ref).abs().max().item() <= 1e-12 * ref.abs().max().item()
+    for t in (0, 500, 999):
+        ref = to.thermalize(sd, x[:, :F], noise, t, B, H, W)
+        got = to.thermalize_rows(sd, x[:, :F], noise, t, B, H, W)
+        assert got.shape == ref.shape
+        assert (got - ref).abs().max().item() <= 1e-12 * ref.abs().max().item(), t
+    # the pieces the two nets do not use: pooling indices, the gradient-side row operations and the column sum
+    y, idx = to.max_pool_rows(x, B, H, W)
+    img = x.reshape(B, H * W, F + 2)
+    assert torch.equal(torch.gather(img, 1, idx.reshape(B, -1, F + 2)).reshape(y.shape), y)
+    assert torch.equal(to.rows_scale(x, 0.5), 0.5 * x) and torch.equal(to.rows_axpy(x, x, 2.0), 3.0 * x)
+    assert (to.colsum_rows(x) - x.t().sum(1)).abs().max().item() <= 1e-12 * x.abs().sum(0).max().item()
+    mean, rstd, scale, shift = to.group_norm_stats(x, torch.ones(F + 2, dtype=x.dtype), torch.zeros(F + 2, dtype=x.dtype), B, 2)
+    z = to.group_norm_rows(x, torch.ones(F + 2, dtype=x.dtype), torch.zeros(F + 2, dtype=x.dtype), B, 2)
+    assert (to.affine_relu_rows(x, scale, shift, B) - torch.relu(z)).abs().max().item() <= 1e-12
