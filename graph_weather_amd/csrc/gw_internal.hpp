@@ -174,6 +174,14 @@ int edge_fast_launch(int32_t batch, int32_t n_edges, const int32_t* src, const i
                      void* stream);
 size_t edge_fast_carry_bytes(int32_t batch, int32_t n_edges);
 
+// Decoder form of the fp32 edge update without residual (gw_edge_stream.hip): float32 weights, nothing raw, one or two projected
+// fp32-row operands, one middle layer, LayerNorm over 256 features; no residual, no e', no activation saving, atomics mode
+// (the caller checks the last four).
+bool edge_stream_eligible(const gw_operand* x_src, const gw_operand* x_dst, const gw_operand* e_in, const gw_mlp_weights* w);
+int edge_stream_launch(int32_t batch, int32_t n_edges, const int32_t* src, const int32_t* dst, const gw_operand* x_src,
+                       const gw_operand* x_dst, const gw_operand* e_in, const gw_mlp_weights* w, float* agg, int32_t n_dst,
+                       void* stream);
+
 // bf16 edge update with register-resident weights (gw_edge16.hip)
 bool edge16_eligible(const gw_operand* x_src, const gw_operand* x_dst, const gw_operand* e_in, const gw_mlp_weights* w);
 size_t edge16_workspace_bytes(int32_t batch, int32_t n_edges);

@@ -1300,9 +1300,12 @@ int gw_edge_update_forward(int32_t batch, int32_t n_edges, const int32_t* src, c
   // shared) e into agg beforehand: sum(LN(.) + e) = sum(LN(.)) + sum(e).  bf16 path with resident weights only (edge16_launch).
   const bool no_res = e_res->k == 0;
   const bool x3 = w->weight_dtype == GW_DTYPE_BF16X3;
-  if (no_res && (e_out_any != nullptr || save || !(x3 || (gw::edge16_eligible(x_src, x_dst, e_in, w) && !(flags & GW_EDGE_DETERMINISTIC)))))
+  // fp32 weights: the no-residual kernel of gw_edge_stream.hip (nothing raw, one or two projected operands, atomics mode)
+  const bool stream32 = no_res && !(flags & (GW_EDGE_DETERMINISTIC | GW_EDGE_SEGMENT_TILES)) && gw::edge_stream_eligible(x_src, x_dst, e_in, w);
+  if (no_res && (e_out_any != nullptr || save || !(x3 || stream32 || (gw::edge16_eligible(x_src, x_dst, e_in, w) && !(flags & GW_EDGE_DETERMINISTIC)))))
     return fail(GW_E_UNSUPPORTED, "gw_edge_update_forward: an edge update without residual (e_res.k == 0) is implemented for the bf16 "
-                                  "path with resident weights (atomics mode) and for bf16x3 weights, without e_out or activation saving");
+                                  "path with resident weights (atomics mode), for bf16x3 weights and for float32 weights with projected "
+                                  "operands only (one middle layer, LayerNorm over 256, atomics mode), without e_out or activation saving");
   if (!no_res && (e_res->k != 256 || e_res->ld % 4 != 0 || !e_res->ptr))
     return fail(GW_E_UNSUPPORTED, "gw_edge_update_forward: e_res (residual edge features) must be 256 wide");
   // edge tiles (bf16) are a format of the bf16 path with resident weights only
@@ -1335,6 +1338,7 @@ int gw_edge_update_forward(int32_t batch, int32_t n_edges, const int32_t* src, c
     return gw::edge16_launch(batch, n_edges, src, dst, x_src, x_dst, e_in, e_res, w, nullptr, tiles_out ? e_out_any : nullptr, agg, n_dst,
                              workspace, flags, stream);
   }
+  if (stream32) return gw::edge_stream_launch(batch, n_edges, src, dst, x_src, x_dst, e_in, w, agg, n_dst, stream);
   const size_t ws16 = gw::edge16_workspace_needed(batch, n_edges, e_in, det);
   if (det && save) return fail(GW_E_UNSUPPORTED, "gw_edge_update_forward: deterministic segment sums are an inference option");
   if (tiles_in || tiles_out || (no_res && !x3) || half_nodes) {

@@ -1024,8 +1024,10 @@ class AssimilatorDecoder(nn.Module):
             return None  # (the frozen bf16 mode keeps its own table formats and is left as it is)
         key_e = _version_key(list(self.edge_encoder.parameters()))
         key = _version_key(list(self.edge_encoder.parameters()) + list(blk.parameters()))
-        if self._cache.fresh("dec_e", key_e) and self._cache.fresh("dec_pe", key):
+        # (fp32 without residual: the product of the sums of e is the third such table; the route is asked only on a miss)
+        if self._cache.fresh("dec_e", key_e) and self._cache.fresh("dec_pe", key) and (self._cache.fresh("dec_e_sum", key) or not self.stream_path()):
             return None
+        stream = self.stream_path()
         plan = self._plan(dev)
         n_e = plan.num_edges
         if n_e == 0:
@@ -1037,7 +1039,10 @@ class AssimilatorDecoder(nn.Module):
             e = self.edge_embedding(plan)
             pm_e = mlp_e.packed()
             pe = self._cache.get("dec_pe", key, lambda: ops.project_forward([pm_e.w1[2]], Operand(e, n_e, 256), n_e, n_e)[0])
-        for t in (e, pe):
+            made = [e, pe]
+            if stream:
+                made.append(self._e_sum_product(plan, e, key, False))
+        for t in made:
             t.record_stream(main)  # made on the side stream, read on the caller's for as long as the cache entry lives
         return side
 
@@ -1057,6 +1062,33 @@ class AssimilatorDecoder(nn.Module):
             return routes.BLOCK_ROWS
         return routes.block_route(_form(mlp_e), mlp_n.compute_dtype, self.graphs.dec_plan.num_edges, False, False,
                                   bool(blk.deterministic))
+
+    def stream_path(self) -> bool:
+        """float32 inference on the decoder-form edge kernel without residual (``routes.decoder_stream``).  Decided from the
+        modules' shapes alone (native 256 widths, LayerNorm, two hidden layers - the condition of the hand-scheduled fp32 edge
+        kernel in ``set_deterministic``), so asking packs no weights."""
+        blk = self.graph_processor.blocks[0]
+        mlp_e, mlp_n = blk.edge_model.edge_mlp, blk.node_model.node_mlp
+        if mlp_e.compute_dtype != torch.float32 or wide.decoder_is_wide(self):
+            return False
+        native = not mlp_e._layout()[4] and mlp_e._norm() is not None and len(mlp_e._linears()) == 3
+        form = routes.MlpForm(torch.float32, 1 if native else -1, 0 if native else -1, native)
+        return routes.decoder_stream(form, mlp_n.compute_dtype, self.graphs.dec_plan.num_edges, False, _autograd_on(self),
+                                     bool(blk.deterministic), bool(ops.EDGE_STREAM))
+
+    def _e_sum_product(self, plan: GraphPlan, e_rows: torch.Tensor, key, half: bool) -> torch.Tensor:
+        """Wa . S, S[dst] = sum of the (batch-shared) edge embedding over the destination's edges: the cached, batch-shared
+        projected operand that stands in the node update for the residual the edge update no longer adds (see ``decode``)."""
+        pm_n = self.graph_processor.blocks[0].node_model.node_mlp.packed()
+        n_e = plan.num_edges
+
+        def make_e_sum():
+            e_sum = ag.segment_sum_rows(e_rows, n_e, 1, 1, plan.n_dst, plan.dst_ptr(), None)
+            # (bf16 mode: fp16 rows, like every layer-1 product of that path: the node update adds them to its fp32
+            # accumulator and rounds the sum to bf16; fp32 / bf16x3: fp32 rows)
+            return ops.project_forward([pm_n.w1[1]], Operand(e_sum, plan.n_dst, 256), plan.n_dst, plan.n_dst, out_half=half)[0]
+
+        return self._cache.get("dec_e_sum", key, make_e_sum)
 
     def split_path(self) -> bool:
         """Inference with bf16x3 (split-operand) products in both MLPs of the decoder block (see ``Encoder.split_path``)."""
@@ -1102,9 +1134,9 @@ class AssimilatorDecoder(nn.Module):
                 pe = self._cache.get("dec_pe_pad", key, lambda: seg.pad_rows(pe_rows))
             x_node = FEED_ZERO
             x3 = self.split_path()
-            if x3 or routes.resident_bf16(_form(mlp_e), n_e):
-                pm_n = blk.node_model.node_mlp.packed()
-                if not (team or x3):
+            stream = self.stream_path()
+            if x3 or stream or routes.resident_bf16(_form(mlp_e), n_e):
+                if not (team or x3 or stream):
                     # residual of the resident bf16 kernel: the cached edge embedding as one shared set of bf16 edge tiles
                     e = self._cache.get("dec_e_tiles", key, lambda: ops.edge_rows_to_tiles(e_rows, 1, n_e, n_e))
                 else:
@@ -1112,14 +1144,8 @@ class AssimilatorDecoder(nn.Module):
                     #   agg = sum(LN(.) + e) = sum(LN(.)) + S,  S[dst] = sum of e over the destination's edges (batch independent),
                     # and layer 1 of the node update (graph_net_block.py:189, x == 0) is Wa.agg = Wa.sum(LN(.)) + Wa.S: the edge
                     # kernel adds no residual at all, and Wa.S enters the node update as a cached, batch-shared PROJECTED operand
-                    # in the slot of the all-zero x rows.
-                    def make_e_sum():
-                        e_sum = ag.segment_sum_rows(e_rows, n_e, 1, 1, plan.n_dst, plan.dst_ptr(), None)
-                        # (bf16 mode: fp16 rows, like every layer-1 product of that path: the node update adds them to its fp32
-                        # accumulator and rounds the sum to bf16; bf16x3: fp32 rows)
-                        return ops.project_forward([pm_n.w1[1]], Operand(e_sum, plan.n_dst, 256), plan.n_dst, plan.n_dst, out_half=team)[0]
-
-                    x_node = Feed(self._cache.get("dec_e_sum", key, make_e_sum), 0, "proj")
+                    # in the slot of the all-zero x rows.  (bf16 team path, bf16x3, and fp32 on the no-residual edge kernel.)
+                    x_node = Feed(self._e_sum_product(plan, e_rows, key, team), 0, "proj")
                     e = None
         res = None
         if residual is not None:

@@ -44,6 +44,11 @@ class KernelTimer:
 
 TIMER: Optional[KernelTimer] = None
 
+EDGE_STREAM = True
+"""float32 inference: the decoder's edge update runs without the per-edge residual on the decoder-form kernel of
+csrc/gw_edge_stream.hip (the segment sums of the batch-shared edge embedding enter the node update as a cached product).
+``False`` forces the per-edge residual route on ``edge_kernel`` (csrc/gw_edge.hip).  Read on every ``decode``."""
+
 
 def _stream(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream

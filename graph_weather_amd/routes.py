@@ -35,7 +35,7 @@ class MlpForm:
 
 
 EDGE_AUTOGRAD = "autograd"        # differentiable path (autograd.py): fp32 / bf16x3 kernels that also write activation saves
-EDGE_ROWS_FP32 = "rows_fp32"      # csrc/gw_edge.hip (edge_kernel) / chain_kernel: fp32 rows in, fp32 rows out
+EDGE_ROWS_FP32 = "rows_fp32"      # csrc/gw_edge.hip (edge_kernel) / gw_edge_stream.hip (no residual) / chain_kernel: fp32 rows
 EDGE_ROWS_X3 = "rows_bf16x3"      # csrc/gw_split.hip: the same tables, split-operand products
 EDGE_TILES_BF16 = "tiles_bf16"    # frozen budget mode: resident-weight kernels, per-sample edge features as bf16 edge tiles
 EDGE_ROWS_BF16 = "rows_bf16"      # frozen budget mode, shapes the resident kernels do not take: streaming bf16 kernel on rows
@@ -86,6 +86,17 @@ def block_route(edge: MlpForm, node_dtype, n_edges: int, wide: bool, autograd: b
     if edge.dtype == torch.bfloat16 and node_dtype == torch.bfloat16 and not deterministic and resident_bf16(edge, n_edges):
         return BLOCK_TEAM
     return BLOCK_ROWS
+
+
+def decoder_stream(edge: MlpForm, node_dtype, n_edges: int, wide: bool, autograd: bool, deterministic: bool, enabled: bool) -> bool:
+    """The decoder block runs without residual on the decoder-form fp32 edge kernel (csrc/gw_edge_stream.hip): float32 inference
+    in both MLPs, one middle layer, LayerNorm over all 256 features, atomics mode, and the switch ``ops.EDGE_STREAM`` on.  The
+    sums of e then enter the node update as a cached table, as on BLOCK_TEAM / BLOCK_SPLIT.  Training, deterministic mode and
+    every other shape keep the per-edge residual (BLOCK_ROWS on ``edge_kernel``)."""
+    if not enabled or wide or autograd or deterministic or n_edges <= 0:
+        return False
+    return (edge.dtype == torch.float32 and node_dtype == torch.float32 and edge.n_mid == 1 and edge.ln_width == 0
+            and edge.has_norm)
 
 
 # ---- the processor stack ------------------------------------------------------------------------------------------------

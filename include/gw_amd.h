@@ -285,7 +285,9 @@ int gw_project_forward(int64_t n_rows, int32_t rows_per_batch, const gw_operand*
  * raw rows, pre-projected rows (operand.projected) or zeros (k == 0); e_res is the raw edge feature row (the residual of
  * graph_net_block.py:135) - or k == 0 for "none": a caller that wants only the aggregate of batch-shared edge features (the
  * decoder, assimilator_decoder.py:195 drops e') may add their per-destination sums into agg beforehand instead,
- * sum(LN(.) + e) = sum(LN(.)) + sum(e)  (bf16 weights with resident kernels in atomics mode, or bf16x3 weights; e_out == NULL, no save). */
+ * sum(LN(.) + e) = sum(LN(.)) + sum(e)  (bf16 weights with resident kernels in atomics mode, or bf16x3 weights, or float32
+ * weights with nothing raw, one or two projected fp32-row operands, one middle layer, LayerNorm over 256 features, atomics mode - the
+ * decoder-form kernel of csrc/gw_edge_stream.hip; e_out == NULL, no save). */
 int gw_edge_update_forward(int32_t batch, int32_t n_edges, const int32_t* src, const int32_t* dst,
                            const gw_operand* x_src, const gw_operand* x_dst, const gw_operand* e_in,
                            const gw_operand* e_res, const gw_mlp_weights* w,

@@ -21,7 +21,7 @@ agg = collections.defaultdict(lambda: [0.0, 0])
 with open(sys.argv[1]) as fh:
     for r in csv.DictReader(fh):
         k = r.get("Kernel_Name", "")
-        m = re.search(r"(chain_kernel|edge_kernel)<[^>]*>", k)
+        m = re.search(r"(chain_kernel|edge_kernel|estream_kernel)<[^>]*>", k)
         if not m: continue
         key = (m.group(0), r.get("Grid_Size"), r["Counter_Name"])
         agg[key][0] += float(r["Counter_Value"]); agg[key][1] += 1
@@ -35,7 +35,7 @@ run_pass grbm GRBM_GUI_ACTIVE GRBM_COUNT
 run_pass fetch FETCH_SIZE
 run_pass write WRITE_SIZE
 [ "${PMC_LDS:-1}" = "1" ] && run_pass lds SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_VMEM
-# summary JSON of the dominant kernel (decoder edge update = the edge_kernel launch with the largest grid); bench.py reads
+# summary JSON of the dominant kernel (decoder edge update = the estream_kernel / edge_kernel launch with the largest grid); bench.py reads
 # the committed copy (profiles/pmc_decoder_edge.json) for roofline.traffic
 python - $GRAFT_REPO_ROOT/$OUT <<'PY'
 import json, sys, os, re
@@ -50,7 +50,8 @@ def load(name):
     return rows
 r = {}
 for n in ("sq", "grbm", "fetch", "write", "lds"): r.update(load(n))
-edge = [(g, k) for (k, g, c) in r if k.startswith("edge_kernel")]
+# (fp32 inference runs the decoder's launch on estream_kernel - csrc/gw_edge_stream.hip - the other edge updates on edge_kernel)
+edge = [(g, k) for (k, g, c) in r if k.startswith("estream_kernel")] or [(g, k) for (k, g, c) in r if k.startswith("edge_kernel")]
 if edge:
     g, k = max(edge)
     get = lambda c: r.get((k, g, c))
