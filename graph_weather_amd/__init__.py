@@ -41,6 +41,18 @@ from .cafa import (  # noqa: F401  (csrc/gw_cafa.hip, axial addressing of csrc/g
     FactorizedAttention,
     FactorizedTransformerBlock,
 )
+from .aurora import (  # noqa: F401  (csrc/gw_aurora.hip, csrc/gw_conv3d.hip, masked attention of csrc/gw_fengwu.hip)
+    AuroraModel,
+    Decoder3D,
+    EarthSystemLoss,
+    PerceiverProcessor,
+    PointCloudProcessor,
+    PointDecoder,
+    PointEncoder,
+    ProcessorConfig,
+    SelfAttentionLayer,
+    Swin3DEncoder,
+)
 from .graphed import ForwardGraph  # noqa: F401  (the inference forward as one HIP graph)
 from .rollout import rollout  # noqa: F401
 from .optim import AdamW  # noqa: F401

@@ -41,6 +41,12 @@ EXPORTS = [
     "gw_attention_axial_forward", "gw_attention_axial_backward",
     "gw_patch_workspace_bytes", "gw_patch_embed_forward", "gw_patch_embed_backward", "gw_patch_expand_forward",
     "gw_patch_expand_backward",
+    "gw_attention_masked_forward", "gw_attention_masked_backward",
+    "gw_earth_loss_workspace_bytes", "gw_earth_loss_forward", "gw_earth_loss_backward",
+    "gw_token_mean_forward", "gw_token_mean_backward", "gw_relu_forward", "gw_row_scale",
+    "gw_conv3d_workspace_bytes", "gw_conv3d_forward", "gw_conv3d_backward",
+    "gw_gemm_tn_ordered_workspace_bytes", "gw_gemm_tn_ordered", "gw_layernorm_backward_ordered_workspace_bytes",
+    "gw_layernorm_backward_ordered",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -353,6 +359,46 @@ def lib():
     L.gw_patch_expand_backward.restype = c_int
     L.gw_patch_expand_backward.argtypes = [c_int32] * 6 + [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_int32,
                                                            c_void_p, c_void_p, c_void_p]
+    L.gw_attention_masked_forward.restype = c_int
+    L.gw_attention_masked_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
+                                              c_void_p, c_float, c_void_p, POINTER(c_int64), c_void_p, c_void_p]
+    L.gw_attention_masked_backward.restype = c_int
+    L.gw_attention_masked_backward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
+                                               c_void_p, c_float, c_void_p, POINTER(c_int64), c_void_p, POINTER(c_int64), c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]
+    L.gw_earth_loss_workspace_bytes.restype = c_size_t
+    L.gw_earth_loss_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.gw_earth_loss_forward.restype = c_int
+    L.gw_earth_loss_forward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_float,
+                                        c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_earth_loss_backward.restype = c_int
+    L.gw_earth_loss_backward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_float, c_float, c_float,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_token_mean_forward.restype = c_int
+    L.gw_token_mean_forward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]
+    L.gw_token_mean_backward.restype = c_int
+    L.gw_token_mean_backward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]
+    L.gw_relu_forward.restype = c_int
+    L.gw_relu_forward.argtypes = [c_int64, c_void_p, c_void_p, c_void_p]
+    L.gw_row_scale.restype = c_int
+    L.gw_row_scale.argtypes = [c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]
+    L.gw_conv3d_workspace_bytes.restype = c_size_t
+    L.gw_conv3d_workspace_bytes.argtypes = [c_int32] * 7
+    L.gw_conv3d_forward.restype = c_int
+    L.gw_conv3d_forward.argtypes = [c_int32] * 7 + [c_void_p, POINTER(c_int64), c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]
+    L.gw_conv3d_backward.restype = c_int
+    L.gw_conv3d_backward.argtypes = [c_int32] * 7 + [c_void_p, POINTER(c_int64), c_void_p, c_void_p, POINTER(c_int64), c_void_p, c_size_t,
+                                                     c_void_p, POINTER(c_int64), c_void_p, c_void_p, c_void_p]
+    L.gw_gemm_tn_ordered_workspace_bytes.restype = c_size_t
+    L.gw_gemm_tn_ordered_workspace_bytes.argtypes = [c_int32, c_int32, c_int64]
+    L.gw_gemm_tn_ordered.restype = c_int
+    L.gw_gemm_tn_ordered.argtypes = [c_int32, c_int32, c_int64, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_size_t, c_void_p, c_int32,
+                                     c_void_p, c_void_p]
+    L.gw_layernorm_backward_ordered_workspace_bytes.restype = c_size_t
+    L.gw_layernorm_backward_ordered_workspace_bytes.argtypes = [c_int64, c_int32]
+    L.gw_layernorm_backward_ordered.restype = c_int
+    L.gw_layernorm_backward_ordered.argtypes = [c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
+                                                c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

@@ -67,6 +67,7 @@ struct AttnArgs {
   float *dq, *dk, *dv;
   int64_t sd[3];  // dq, dk, dv
   int vec;  // every pointer 16-byte aligned, every stride and dim_head a multiple of 4
+  const float* bias;  // MASKED kernels: [batch, n] added to the scaled scores of every head and query of a sequence, 0 or -inf per key
 };
 
 template <int DP>
@@ -171,6 +172,7 @@ struct Place {
   bool ok;        // the pair exists
   int o, s;       // its sequence
   int h;
+  int64_t seq;    // o * inner + s: the row of the key bias
   // offset in floats of token 0 of the sequence in an operand with strides st; the head offset h d is added by the caller
   __device__ __forceinline__ int64_t at(const int64_t (&st)[3]) const { return o * st[0] + s * st[1]; }
 };
@@ -191,12 +193,13 @@ __device__ __forceinline__ Place place_of(const AttnArgs& a, int wave) {
   p.h = (int)(pr - b * a.heads);
   p.o = (int)(b / a.inner);
   p.s = (int)(b - (int64_t)p.o * a.inner);
+  p.seq = b;
   return p;
 }
 
 // ---- forward -----------------------------------------------------------------------------------------------------------
-template <int DP, bool PACKED>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs a) {
+template <int DP, bool PACKED, bool MASKED>
+__device__ __forceinline__ void attn_fwd_body(const AttnArgs& a) {
   constexpr int LD = Cfg<DP>::LD, NC = Cfg<DP>::NC, TB = PACKED ? 16 : Cfg<DP>::TB, NT = TB / 16;
   constexpr int LROWS = PACKED ? 16 * Cfg<DP>::PW : TB;
   __shared__ __attribute__((aligned(16))) float Ks[LROWS * LD];
@@ -241,18 +244,28 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float sc = scaled(s[t][r], a.scale);
-        const float v = (k0 + 16 * t + 4 * kq + r < n) ? sc : -INFINITY;  // the ragged tail of the keys
+        const int key = k0 + 16 * t + 4 * kq + r;
+        float v = (key < n) ? sc : -INFINITY;  // the ragged tail of the keys
+        if constexpr (MASKED) {
+          if (key < n && pl.ok) v += ldg1(a.bias + pl.seq * n + key);  // 0 or -inf
+        }
         s[t][r] = v;
         mx = fmaxf(mx, v);
       }
-    const float m_new = fmaxf(m, group_max(mx));  // finite: key k0 is valid
-    const float alpha = expf(m - m_new);          // 0 on the first tile (m = -inf)
+    float m_new = fmaxf(m, group_max(mx));  // finite: key k0 is valid
+    float m_ref = m_new;                    // what the exponents are taken against
+    if constexpr (MASKED) {
+      // every key so far masked: the maximum is still -inf, and -inf - -inf is NaN.  Against 0 every p and alpha are exp(-inf) = 0
+      // and the running state stays (m, l, o) = (-inf, 0, 0) until the first kept key arrives.
+      if (m_new == -INFINITY) m_ref = 0.f;
+    }
+    const float alpha = expf(m - m_ref);          // 0 on the first tile (m = -inf)
     float rs = 0.f;
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = expf(s[t][r] - m_new);
+        const float p = expf(s[t][r] - m_ref);
         s[t][r] = p;
         rs += p;
       }
@@ -302,8 +315,8 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(const AttnArgs a) {
 }
 
 // ---- dQ: queries stationary, keys streamed ----------------------------------------------------------------------------------
-template <int DP, bool PACKED>
-__global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs a) {
+template <int DP, bool PACKED, bool MASKED>
+__device__ __forceinline__ void attn_dq_body(const AttnArgs& a) {
   constexpr int LD = Cfg<DP>::LD, NC = Cfg<DP>::NC, TB = PACKED ? 16 : Cfg<DP>::TB, NT = TB / 16;
   constexpr int LROWS = PACKED ? 16 * Cfg<DP>::PW : TB;
   __shared__ __attribute__((aligned(16))) float Ks[LROWS * LD];
@@ -355,8 +368,12 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs a) {
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const bool kok = k0 + 16 * t + 4 * kq + r < n;
-        const float sc = scaled(s[t][r], a.scale);
+        const int key = k0 + 16 * t + 4 * kq + r;
+        const bool kok = key < n;
+        float sc = scaled(s[t][r], a.scale);
+        if constexpr (MASKED) {
+          if (kok && pl.ok) sc += ldg1(a.bias + pl.seq * n + key);  // -inf: p = exp(-inf) = 0
+        }
         const float p = kok ? expf((sc - mrow) - lrow) : 0.f;
         s[t][r] = p * (dp[t][r] - delta) * a.scale;  // dS
       }
@@ -370,8 +387,8 @@ __global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs a) {
 }
 
 // ---- dK, dV: keys stationary (accumulators resident), queries streamed ------------------------------------------------------------
-template <int DP, bool PACKED>
-__global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) {
+template <int DP, bool PACKED, bool MASKED>
+__device__ __forceinline__ void attn_dkv_body(const AttnArgs& a) {
   constexpr int LD = Cfg<DP>::LD, NC = Cfg<DP>::NC, TB = PACKED ? 16 : Cfg<DP>::TB, NT = TB / 16;
   constexpr int LROWS = PACKED ? 16 * Cfg<DP>::PW : TB;
   __shared__ __attribute__((aligned(16))) float Qs[LROWS * LD];
@@ -399,6 +416,10 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) {
   }
   const float* qbase = pl.ok ? a.q + bq + col : nullptr;
   const float* gbase = pl.ok ? a.dout + pl.at(a.sg) + col : nullptr;
+  float kbias = 0.f;  // of this lane's key: -inf makes its p, and with it dK and dV, exactly zero
+  if constexpr (MASKED) {
+    if (kok) kbias = ldg1(a.bias + pl.seq * n + krow);
+  }
   const int off = PACKED ? wave * 16 : 0;
   float* qs = Qs + off * LD;
   float* gs = Gs + off * LD;
@@ -442,7 +463,8 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) {
       const f32x4 d4 = *(const f32x4*)(ds + 16 * t + 4 * kq);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float sc = scaled(s[t][r], a.scale);
+        float sc = scaled(s[t][r], a.scale);
+        if constexpr (MASKED) sc += kbias;
         const float p = kok ? expf((sc - m4[r]) - l4[r]) : 0.f;
         s[t][r] = p;
         dp[t][r] = p * (dp[t][r] - d4[r]) * a.scale;  // dS
@@ -462,6 +484,21 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) {
     }
   }
 }
+
+// The kernels proper: the unmasked ones keep their names and template signature <DP, PACKED>; the MASKED ones (a key bias, see
+// AttnArgs::bias) are kernels of their own.
+template <int DP, bool PACKED>
+__global__ __launch_bounds__(256) void attn_fwd_kernel(const AttnArgs a) { attn_fwd_body<DP, PACKED, false>(a); }
+template <int DP, bool PACKED>
+__global__ __launch_bounds__(256) void attn_dq_kernel(const AttnArgs a) { attn_dq_body<DP, PACKED, false>(a); }
+template <int DP, bool PACKED>
+__global__ __launch_bounds__(256) void attn_dkv_kernel(const AttnArgs a) { attn_dkv_body<DP, PACKED, false>(a); }
+template <int DP, bool PACKED>
+__global__ __launch_bounds__(256) void attn_fwd_masked_kernel(const AttnArgs a) { attn_fwd_body<DP, PACKED, true>(a); }
+template <int DP, bool PACKED>
+__global__ __launch_bounds__(256) void attn_dq_masked_kernel(const AttnArgs a) { attn_dq_body<DP, PACKED, true>(a); }
+template <int DP, bool PACKED>
+__global__ __launch_bounds__(256) void attn_dkv_masked_kernel(const AttnArgs a) { attn_dkv_body<DP, PACKED, true>(a); }
 
 template <typename F>
 int by_dim_head(int d, F f) {
@@ -598,7 +635,12 @@ int attn_forward_launch(AttnArgs& a, void* stream) {
   const dim3 grid(attn_grid(a, packed));
   by_dim_head(a.d, [&](auto dp) {
     constexpr int DP = decltype(dp)::value;
-    if (packed)
+    if (a.bias != nullptr) {
+      if (packed)
+        hipLaunchKernelGGL((attn_fwd_masked_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
+      else
+        hipLaunchKernelGGL((attn_fwd_masked_kernel<DP, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+    } else if (packed)
       hipLaunchKernelGGL((attn_fwd_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
     else
       hipLaunchKernelGGL((attn_fwd_kernel<DP, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
@@ -617,7 +659,15 @@ int attn_backward_launch(AttnArgs& a, void* stream) {
   const dim3 grid(attn_grid(a, packed));
   by_dim_head(a.d, [&](auto dp) {
     constexpr int DP = decltype(dp)::value;
-    if (packed) {
+    if (a.bias != nullptr) {
+      if (packed) {
+        hipLaunchKernelGGL((attn_dkv_masked_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((attn_dq_masked_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
+      } else {
+        hipLaunchKernelGGL((attn_dkv_masked_kernel<DP, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL((attn_dq_masked_kernel<DP, false>), grid, dim3(256), 0, (hipStream_t)stream, a);
+      }
+    } else if (packed) {
       hipLaunchKernelGGL((attn_dkv_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
       hipLaunchKernelGGL((attn_dq_kernel<DP, true>), grid, dim3(64 * Cfg<DP>::PW), 0, (hipStream_t)stream, a);
     } else {
@@ -655,6 +705,36 @@ int gw_attention_axial_backward(int32_t outer, int32_t inner, int32_t heads, int
   int rc = axial_args(a, "gw_attention_axial_backward", outer, inner, heads, n, dim_head);
   if (rc != GW_OK) return rc;
   a.q = q, a.k = k, a.v = v, a.scale = scale, a.out = const_cast<float*>(out), a.lse = const_cast<float*>(lse);
+  a.dout = dout, a.delta = delta, a.dq = dq, a.dk = dk, a.dv = dv;
+  set3(a.sq, stride_qkv), set3(a.so, stride_out), set3(a.sg, stride_dout), set3(a.sd, stride_dqkv);
+  return attn_backward_launch(a, stream);
+}
+
+// the axial entry points with a key bias [outer * inner, n] (0 keeps a key, -inf drops it for every query and head of its sequence)
+int gw_attention_masked_forward(int32_t outer, int32_t inner, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k,
+                                const float* v, const int64_t* stride_qkv, const float* key_bias, float scale, float* out,
+                                const int64_t* stride_out, float* lse, void* stream) {
+  if (!q || !k || !v || !out || !lse || !stride_qkv || !stride_out || !key_bias)
+    return failf(GW_E_BADARG, "gw_attention_masked_forward: bad arguments");
+  AttnArgs a = {};
+  int rc = axial_args(a, "gw_attention_masked_forward", outer, inner, heads, n, dim_head);
+  if (rc != GW_OK) return rc;
+  a.q = q, a.k = k, a.v = v, a.scale = scale, a.out = out, a.lse = lse, a.bias = key_bias;
+  set3(a.sq, stride_qkv), set3(a.so, stride_out);
+  return attn_forward_launch(a, stream);
+}
+
+int gw_attention_masked_backward(int32_t outer, int32_t inner, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k,
+                                 const float* v, const int64_t* stride_qkv, const float* key_bias, float scale, const float* out,
+                                 const int64_t* stride_out, const float* dout, const int64_t* stride_dout, const float* lse, float* delta,
+                                 float* dq, float* dk, float* dv, const int64_t* stride_dqkv, void* stream) {
+  if (!q || !k || !v || !out || !dout || !lse || !delta || !dq || !dk || !dv || !stride_qkv || !stride_out || !stride_dout || !stride_dqkv ||
+      !key_bias)
+    return failf(GW_E_BADARG, "gw_attention_masked_backward: bad arguments");
+  AttnArgs a = {};
+  int rc = axial_args(a, "gw_attention_masked_backward", outer, inner, heads, n, dim_head);
+  if (rc != GW_OK) return rc;
+  a.q = q, a.k = k, a.v = v, a.scale = scale, a.out = const_cast<float*>(out), a.lse = const_cast<float*>(lse), a.bias = key_bias;
   a.dout = dout, a.delta = delta, a.dq = dq, a.dk = dk, a.dv = dv;
   set3(a.sq, stride_qkv), set3(a.so, stride_out), set3(a.sg, stride_dout), set3(a.sd, stride_dqkv);
   return attn_backward_launch(a, stream);

@@ -722,6 +722,77 @@ int gw_patch_expand_backward(int32_t batch, int32_t channels, int32_t h, int32_t
                              int32_t ld_rows, const float* weight, const float* dout, void* workspace, size_t workspace_bytes,
                              float* d_rows, int32_t ld_drows, float* dweight, float* dbias, void* stream);
 
+/* =====================================================================================================================
+ * Aurora (graph_weather/models/aurora), csrc/gw_aurora.hip and the MASKED attention kernels of csrc/gw_fengwu.hip.
+ * All fp32, no atomics, every sum in one fixed order (bitwise reproducible), no host synchronisation.
+ *
+ * Key-padding masks: gw_attention_axial_forward / _backward with key_bias [outer * inner, n] added to the scaled scores of
+ * every head and query of a sequence - 0 keeps a key, -inf drops it.  A leading run of dropped keys leaves the online softmax
+ * at (maximum, sum, output) = (-inf, 0, 0) without NaN; dk and dv of a dropped key are exactly zero; an all-zero bias gives the
+ * bits of the unmasked entry points.  A sequence whose keys are all dropped is NaN, as in torch. */
+int gw_attention_masked_forward(int32_t outer, int32_t inner, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k,
+                                const float* v, const int64_t* stride_qkv, const float* key_bias, float scale, float* out,
+                                const int64_t* stride_out, float* lse, void* stream);
+int gw_attention_masked_backward(int32_t outer, int32_t inner, int32_t heads, int32_t n, int32_t dim_head, const float* q, const float* k,
+                                 const float* v, const int64_t* stride_qkv, const float* key_bias, float scale, const float* out,
+                                 const int64_t* stride_out, const float* dout, const int64_t* stride_dout, const float* lse, float* delta,
+                                 float* dq, float* dk, float* dv, const int64_t* stride_dqkv, void* stream);
+/* EarthSystemLoss (model.py): pred, target [batch, n, channels], points [batch, n, 2] (longitude, latitude in degrees), dense.
+ *   mse       mean (pred - target)^2                                   (target NULL: 0)
+ *   spatial   mean over [n, n, channels] of m_ij ((pred_i - target_i) - (pred_j - target_j))^2, m_ij = 1 where points i and j
+ *             are closer than 5 degrees; `spatial` != 0 asks for it and needs batch == 1 (the reference cannot form it
+ *             otherwise) and channels <= 128 (GW_E_UNSUPPORTED above); pairs are walked in tiles, nothing n x n is written.
+ *             pair_rows [n, channels] receives G_i = sum_j m_ij (e_i - e_j): the gradient is 4 G / (n^2 channels).
+ *   physical  mean relu(-pred) + mean relu(pred - 500) + 0.1 mean_r relu(pred[r, 0] - (1 - |lat_r| / 90) mean(pred))
+ *   total     alpha mse + beta spatial + gamma physical
+ * out = (total, mse, spatial, physical); stats [2] is kept for the backward (the mean of pred and the sum of the active
+ * latitude weights).  workspace: gw_earth_loss_workspace_bytes (host-side query, 0 with the error set on bad arguments), 8-byte
+ * aligned: per-workgroup fp64 partials added in workgroup order.
+ * gw_earth_loss_backward: gout [4] = upstream gradients of the four scalars (on the device); dpred and / or dtarget. */
+size_t gw_earth_loss_workspace_bytes(int32_t batch, int32_t n, int32_t channels);
+int gw_earth_loss_forward(int32_t batch, int32_t n, int32_t channels, const float* pred, const float* target, const float* points,
+                          int32_t spatial, float alpha, float beta, float gamma, void* workspace, size_t workspace_bytes, float* out,
+                          float* pair_rows, float* stats, void* stream);
+int gw_earth_loss_backward(int32_t batch, int32_t n, int32_t channels, const float* pred, const float* target, const float* points,
+                           int32_t spatial, float alpha, float beta, float gamma, const float* pair_rows, const float* stats,
+                           const float* gout, float* dpred, float* dtarget, void* stream);
+/* out[b, :width] = mean over the `tokens` rows of sample b of x [batch * tokens, width]; dx[(b, s)] = dout[b] / tokens. */
+int gw_token_mean_forward(int32_t batch, int32_t tokens, int32_t width, const float* x, int32_t ld_x, float* out, int32_t ld_out,
+                          void* stream);
+int gw_token_mean_backward(int32_t batch, int32_t tokens, int32_t width, const float* dout, int32_t ld_dout, float* dx, int32_t ld_dx,
+                           void* stream);
+/* y = max(x, 0) on n floats (its gradient is gw_relu_backward on the output). */
+int gw_relu_forward(int64_t n, const float* x, float* y, void* stream);
+/* out[r, :width] = x[r, :width] * row_factor[r] (a per-point mask; its gradient is the same call on dout). */
+int gw_row_scale(int64_t rows, int32_t width, const float* x, int32_t ld_x, const float* row_factor, float* out, int32_t ld_out,
+                 void* stream);
+/* Weight gradients in one fixed order (the training kernels above add their row slabs with float atomics): per-slab partials in the
+ * caller's workspace (the *_workspace_bytes queries are host side; 0 with the error set on bad arguments), added in slab order.
+ *   gw_gemm_tn_ordered              c[i, j] = sum_r a[r, i] b[r, j] (c [m, n] is overwritten), colsum[i] = sum_r a[r, i] (may be NULL)
+ *   gw_layernorm_backward_ordered   gw_layernorm_backward (eps 1e-5, width <= 4096) with dgamma and dbeta overwritten */
+size_t gw_gemm_tn_ordered_workspace_bytes(int32_t m, int32_t n, int64_t rows);
+int gw_gemm_tn_ordered(int32_t m, int32_t n, int64_t rows, const float* a, int32_t lda, const float* b, int32_t ldb, void* workspace,
+                       size_t workspace_bytes, float* c, int32_t ldc, float* colsum, void* stream);
+size_t gw_layernorm_backward_ordered_workspace_bytes(int64_t rows, int32_t width);
+int gw_layernorm_backward_ordered(int64_t rows, int32_t width, const float* dn, int32_t ld_dn, const float* y, int32_t ld_y,
+                                  const float* gamma, void* workspace, size_t workspace_bytes, float* dy, int32_t ld_dy, float* dgamma,
+                                  float* dbeta, void* stream);
+/* 3 x 3 x 3 convolutions, stride 1, padding 1 (csrc/gw_conv3d.hip): implicit GEMMs on fp32 MFMA, the zero padding a bounds
+ * predicate.  A volume [batch, channels, d, h, w] is addressed by three strides in floats - element (b, c, v = (z h + y) w + x)
+ * at b s[0] + c s[1] + v s[2] - so NCDHW tensors (c d h w, d h w, 1) and channels-last rows [(b, v), c] (d h w ld, 1, ld) are
+ * read and written as they lie.  x has cin channels, out cout.
+ *   transposed 0  nn.Conv3d: weight [cout, cin, 3, 3, 3];   transposed 1  nn.ConvTranspose3d: weight [cin, cout, 3, 3, 3]
+ * bias [cout] may be NULL.  gw_conv3d_backward: dx (may be NULL; laid out by stride_dx), dweight and dbias (both or neither).
+ * The weight and bias gradients are partials per slab of 1024 voxels in gw_conv3d_workspace_bytes (host-side query, 0 with the
+ * error set on bad arguments) of scratch, added in slab order: no atomics, bitwise reproducible. */
+size_t gw_conv3d_workspace_bytes(int32_t batch, int32_t cin, int32_t cout, int32_t d, int32_t h, int32_t w, int32_t transposed);
+int gw_conv3d_forward(int32_t batch, int32_t cin, int32_t cout, int32_t d, int32_t h, int32_t w, int32_t transposed, const float* x,
+                      const int64_t* stride_x, const float* weight, const float* bias, float* out, const int64_t* stride_out,
+                      void* stream);
+int gw_conv3d_backward(int32_t batch, int32_t cin, int32_t cout, int32_t d, int32_t h, int32_t w, int32_t transposed, const float* x,
+                       const int64_t* stride_x, const float* weight, const float* dout, const int64_t* stride_dout, void* workspace,
+                       size_t workspace_bytes, float* dx, const int64_t* stride_dx, float* dweight, float* dbias, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
