@@ -202,14 +202,16 @@ __global__ __launch_bounds__(256) void ln_fwd_wide_kernel(int64_t rows, int widt
     v[j] = c < width ? ldg1(y + (size_t)r * ld_y + c) : 0.f;
     s += v[j];
   }
-  const float inv_n = 1.0f / (float)width;
-  const float mean = wave_sum(s) * inv_n;
+  // a division, not a product with 1 / width: one rounding, so that a row that holds one value has exactly that mean whatever
+  // the width (at zero variance rstd = 316 multiplies whatever the mean is off by)
+  const float mean = wave_sum(s) / (float)width;
   float s2 = 0.f;
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     const float d = (lane + 64 * j < width) ? v[j] - mean : 0.f;
     s2 = fmaf(d, d, s2);
   }
+  const float inv_n = 1.0f / (float)width;
   const float rstd = 1.0f / sqrtf(wave_sum(s2) * inv_n + 1e-5f);
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
@@ -250,7 +252,7 @@ __global__ __launch_bounds__(256) void ln_bwd_wide_kernel(int64_t rows, int widt
       dv[j] = c < width ? ldg1(dn + (size_t)r * ld_dn + c) : 0.f;
       s += yv[j];
     }
-    const float mean = wave_sum(s) * inv_n;
+    const float mean = wave_sum(s) / (float)width;  // the forward's mean: a division (see ln_fwd_wide_kernel)
     float s2 = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
