@@ -182,6 +182,14 @@ int edge_stream_launch(int32_t batch, int32_t n_edges, const int32_t* src, const
                        const gw_operand* x_dst, const gw_operand* e_in, const gw_mlp_weights* w, float* agg, int32_t n_dst,
                        void* stream);
 
+// Inference form of the fast fp32 edge update with the constants in LDS (gw_edge_lds.hip): float32 weights, one middle layer,
+// LayerNorm over 256 features, fp32-row operands - one raw with one or two projected, or three projected; the caller checks
+// that the residual is present as fp32 rows and that the launch saves no activations and runs in atomics mode on row tiles.
+bool edge_lds_eligible(const gw_operand* x_src, const gw_operand* x_dst, const gw_operand* e_in, const gw_mlp_weights* w);
+int edge_lds_launch(int32_t batch, int32_t n_edges, const int32_t* src, const int32_t* dst, const gw_operand* x_src,
+                    const gw_operand* x_dst, const gw_operand* e_in, const gw_operand* e_res, const gw_mlp_weights* w, float* e_out,
+                    float* agg, int32_t n_dst, void* stream);
+
 // bf16 edge update with register-resident weights (gw_edge16.hip)
 bool edge16_eligible(const gw_operand* x_src, const gw_operand* x_dst, const gw_operand* e_in, const gw_mlp_weights* w);
 size_t edge16_workspace_bytes(int32_t batch, int32_t n_edges);

@@ -1348,6 +1348,10 @@ int gw_edge_update_forward(int32_t batch, int32_t n_edges, const int32_t* src, c
     return gw::edge16_launch(batch, n_edges, src, dst, x_src, x_dst, e_in, e_res, w, e_out, tiles_out ? e_out_any : nullptr, agg,
                              n_dst, workspace, det ? GW_EDGE_DETERMINISTIC : 0, stream);
   }
+  // fp32 inference launches of the processor, the encoder and processor block 0: edge_kernel's form with the constants in LDS
+  // (gw_edge_lds.hip; bit for bit edge_kernel's results).  Training, deterministic sums and deeper MLPs keep edge_kernel.
+  if (!save && !det && !seg && !no_res && e_res->layout == GW_LAYOUT_ROWS_F32 && gw::edge_lds_eligible(x_src, x_dst, e_in, w))
+    return gw::edge_lds_launch(batch, n_edges, src, dst, x_src, x_dst, e_in, e_res, w, e_out, agg, n_dst, stream);
   if (w->weight_dtype == GW_DTYPE_F32 && (!save || w->n_mid == 1) && gw::edge_fast_eligible(x_src, x_dst, e_in, w)) {
     if (save && (!save->hidden || !save->pre_norm || save->hidden_ld < 256 || save->hidden_ld % 4 != 0))
       return fail(GW_E_BADARG, "gw_edge_update_forward: bad gw_activation_save");

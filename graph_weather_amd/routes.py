@@ -35,7 +35,7 @@ class MlpForm:
 
 
 EDGE_AUTOGRAD = "autograd"        # differentiable path (autograd.py): fp32 / bf16x3 kernels that also write activation saves
-EDGE_ROWS_FP32 = "rows_fp32"      # csrc/gw_edge.hip (edge_kernel) / gw_edge_stream.hip (no residual) / chain_kernel: fp32 rows
+EDGE_ROWS_FP32 = "rows_fp32"      # csrc/gw_edge.hip (edge_kernel) / gw_edge_lds.hip (its inference form) / gw_edge_stream.hip (no residual) / chain_kernel: fp32 rows
 EDGE_ROWS_X3 = "rows_bf16x3"      # csrc/gw_split.hip: the same tables, split-operand products
 EDGE_TILES_BF16 = "tiles_bf16"    # frozen budget mode: resident-weight kernels, per-sample edge features as bf16 edge tiles
 EDGE_ROWS_BF16 = "rows_bf16"      # frozen budget mode, shapes the resident kernels do not take: streaming bf16 kernel on rows

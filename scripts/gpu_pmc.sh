@@ -21,7 +21,7 @@ agg = collections.defaultdict(lambda: [0.0, 0])
 with open(sys.argv[1]) as fh:
     for r in csv.DictReader(fh):
         k = r.get("Kernel_Name", "")
-        m = re.search(r"(chain_kernel|edge_kernel|estream_kernel)<[^>]*>", k)
+        m = re.search(r"(chain_kernel|edge_kernel|estream_kernel|elds_kernel)<[^>]*>", k)
         if not m: continue
         key = (m.group(0), r.get("Grid_Size"), r["Counter_Name"])
         agg[key][0] += float(r["Counter_Value"]); agg[key][1] += 1

@@ -9,7 +9,7 @@
 # "(bwd_chainx3_kernel|gemm_tn_x3_kernel)<[^>]*>"
 # HBM bytes: FETCH_SIZE x 2 (gfx950 correction, MI355X_MICROARCH.md) and WRITE_SIZE, both in KiB; MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES /
 # 1024 SIMDs / (GRBM_GUI_ACTIVE / 8 XCDs); LDS array utilisation = SQ_LDS_IDX_ACTIVE / 256 CUs / (GRBM_GUI_ACTIVE / 8).
-TAG=${1:-pmc}; CFG=${2:-c2}; RX=${3:-"(chainx3_kernel|chain_kernel|edge_kernel|chain16_kernel|node_rs3?_kernel|edge16[a-z_0-9]*kernel)<[^>]*>"}
+TAG=${1:-pmc}; CFG=${2:-c2}; RX=${3:-"(chainx3_kernel|chain_kernel|edge_kernel|elds_kernel|chain16_kernel|node_rs3?_kernel|edge16[a-z_0-9]*kernel)<[^>]*>"}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -18,8 +18,9 @@ cd /tmp
 run_pass () {
   name=$1; shift
   rm -rf /tmp/pmc_$name
-  GW_AUTO_GRAPH=0 timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d /tmp/pmc_$name -o p -- python $R/bench.py $CMD > $R/$OUT/run_${CFG}_$name.log 2>&1
-  echo "rc=$?" >> $R/$OUT/run_${CFG}_$name.log
+  GW_AUTO_GRAPH=0 timeout -k 10 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d /tmp/pmc_$name -o p -- python $R/bench.py $CMD > $R/$OUT/run_${CFG}_$name.log 2>&1
+  rc=$?; echo "rc=$rc" >> $R/$OUT/run_${CFG}_$name.log
+  if [ $rc -ne 0 ]; then echo "pass $name failed (rc=$rc): no further pass is started"; tail -n 5 $R/$OUT/run_${CFG}_$name.log; exit $rc; fi
   f=$(find /tmp/pmc_$name -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && cp "$f" /tmp/raw_${CFG}_$name.csv
 }
