@@ -47,6 +47,7 @@ EXPORTS = [
     "gw_conv3d_workspace_bytes", "gw_conv3d_forward", "gw_conv3d_backward",
     "gw_gemm_tn_ordered_workspace_bytes", "gw_gemm_tn_ordered", "gw_layernorm_backward_ordered_workspace_bytes",
     "gw_layernorm_backward_ordered",
+    "gw_encoder_fused_forward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -193,6 +194,10 @@ def lib():
     L.gw_edge_update_forward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, POINTER(GwOperand), POINTER(GwOperand),
                                          POINTER(GwOperand), POINTER(GwOperand), POINTER(GwMlpWeights), c_void_p, c_int32, c_void_p,
                                          c_int32, POINTER(GwActivationSave), c_void_p, c_size_t, c_int32, c_void_p]
+    L.gw_encoder_fused_forward.restype = c_int
+    L.gw_encoder_fused_forward.argtypes = [c_int32, c_int32, c_void_p, c_void_p, POINTER(GwOperand), POINTER(GwMlpWeights),
+                                           POINTER(GwOperand), POINTER(GwOperand), POINTER(GwOperand), POINTER(GwMlpWeights), c_void_p,
+                                           c_int32, POINTER(GwActivationSave), c_int32, c_void_p]
     L.gw_edge_tiles_bytes.restype = c_size_t
     L.gw_edge_tiles_bytes.argtypes = [c_int32, c_int32]
     L.gw_edge_rows_to_tiles.restype = c_int

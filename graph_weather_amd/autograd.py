@@ -401,12 +401,18 @@ class RecomputeFunction(torch.autograd.Function):
     training kernels, with their activation saves, which live only until this node's backward returns) and backpropagates
     through that replay.  Gradients of the segment's parameters are returned through autograd like any other."""
 
+    first_pass_depth = 0  # > 0 while the grad-mode-off forward of a segment runs (see in_recomputed_first_pass)
+
     @staticmethod
     def forward(ctx, fn, n_in, params, *tensors):
         ctx.fn, ctx.n_in, ctx.params = fn, n_in, params
         ctx.save_for_backward(*tensors[:n_in])
-        with torch.no_grad():
-            outs = fn(*tensors[:n_in])
+        RecomputeFunction.first_pass_depth += 1
+        try:
+            with torch.no_grad():
+                outs = fn(*tensors[:n_in])
+        finally:
+            RecomputeFunction.first_pass_depth -= 1
         return tuple(outs)
 
     @staticmethod
@@ -422,6 +428,13 @@ class RecomputeFunction(torch.autograd.Function):
         g_in = [next(got, None) if t.requires_grad else None for t in ins]
         g_par = [next(got, None) if p.requires_grad else None for p in params]
         return (None, None, None, *g_in, *g_par)
+
+
+def in_recomputed_first_pass() -> bool:
+    """True inside the grad-mode-off forward of a recomputed segment.  Its values are what the rest of the training step's graph
+    is evaluated at, while the gradients come from the replay on the training kernels: an inference route whose results are not
+    the training route's bits (a different summation order) asks here and keeps the training route's launches."""
+    return RecomputeFunction.first_pass_depth > 0
 
 
 def recompute(fn, inputs: Sequence[torch.Tensor], module) -> Tuple[torch.Tensor, ...]:

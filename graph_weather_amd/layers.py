@@ -790,6 +790,7 @@ class Encoder(nn.Module):
         team = self.team_path(features)
         x3 = self.split_path(features)
         ne = self.node_encoder
+        fused = F == ne.native_k() and self.fused_path(features)
         fused_ps = None
         if ((team and ne.compute_dtype == torch.bfloat16) or (x3 and ne.compute_dtype == BF16X3)) and not ne._layout()[4] \
                 and 32 < ne.native_k() <= 128:
@@ -800,6 +801,8 @@ class Encoder(nn.Module):
             x2 = feats if k <= F else torch.nn.functional.pad(feats, (0, k - F))
             fused_ps = ops.mlp_post_forward(ne.packed(), Operand(x2, G, k), B * G, G, [pm_e0.w1[0]], post_half=team)[1][0]
             xg = None
+        elif fused:
+            xg = None  # (float32 inference: the grid rows stay in the registers of the fused launch below)
         else:
             xg = ne.run(feats, B * G, G)  # grid rows only
         xm = self.mesh_embedding()
@@ -825,6 +828,37 @@ class Encoder(nn.Module):
             seg = enc_plan.seg_tiles(split=True)  # (a polar mesh cell collects hundreds of grid nodes: runs split over tiles)
             if seg is not None:
                 pe = self._cached("enc_pe_pad", list(self.parameters()), lambda: seg.pad_rows(pe))
+        if fused:
+            # float32 inference: node encoder and edge update in ONE launch (csrc/gw_encoder_fused.hip; one edge per grid node, so
+            # the row an edge reads is the row its column can make itself), without residual as on the 16-bit routes above: Wa.S
+            # joins the cached node-update product of the mesh rows.  The block's node update follows as everywhere else.
+            dev = features.device
+            agg = torch.zeros((B * enc_plan.n_dst, 256), dtype=torch.float32, device=dev)
+            # Cold forward (weights changed since the table was made): Wa.S is rebuilt on a SIDE stream underneath the chip-filling
+            # launch - it is first read by the node update behind it, and the segment sums of a polar mesh cell (hundreds of grid
+            # nodes, one wave) are a long tail for a launch of their own in front of it.
+            side = None
+            if not self._cache.fresh("enc_proj_team", _version_key(list(self.parameters()))):
+                main, side = torch.cuda.current_stream(dev), device_stream(dev, "mesh", 0)
+                side.wait_stream(main)  # (behind the projections the table is made from, and whatever still reads the old table)
+            ops.encoder_fused_forward(ne.packed(), blk.edge_model.edge_mlp.packed(), B, enc_plan.src, enc_plan.dst,
+                                      Operand(feats, G, F), Operand(pd_xm, 0, 256, projected=True),
+                                      Operand(pe, 0, 256, projected=True), ops.ZERO, enc_plan.n_dst, agg, tag="encoder_edge")
+            if side is not None:
+                with torch.cuda.stream(side):
+                    px_xm = self._team_node_product(blk, enc_plan, e, px_xm)
+                px_xm.record_stream(main)  # made on the side stream, read on the caller's for as long as the cache entry lives
+                main.wait_stream(side)
+            else:
+                px_xm = self._team_node_product(blk, enc_plan, e, px_xm)
+            pm_n = blk.node_model.node_mlp.packed()
+            n_rows, n_dst = B * enc_plan.n_dst, enc_plan.n_dst
+            x_op, res_x, agg_op = Operand(px_xm, 0, 256, projected=True), Operand(xm, 0, 256), Operand(agg, n_dst, 256)
+            if post_w is not None:
+                agg0 = torch.empty((n_rows, 256), dtype=torch.float32, device=dev)
+                x, posts = ops.node_update_forward(pm_n, n_rows, n_dst, x_op, res_x, agg_op, post_w=post_w, zero_rows=agg0)
+                return x, posts, agg0
+            return ops.node_update_forward(pm_n, n_rows, n_dst, x_op, res_x, agg_op)
         if post_w is not None:
             x, _, posts, agg0 = blk.run(B, enc_plan, x_src, Feed(pd_xm, 0, "proj"), Feed(pe, 0, "proj"), e_res, 0,
                                         Feed(px_xm, 0, "proj"), xm, 0, False, features.device, tag="encoder_edge",
@@ -833,6 +867,25 @@ class Encoder(nn.Module):
         x, _ = blk.run(B, enc_plan, x_src, Feed(pd_xm, 0, "proj"), Feed(pe, 0, "proj"), e_res, 0,
                        Feed(px_xm, 0, "proj"), xm, 0, False, features.device, tag="encoder_edge", seg=seg)
         return x
+
+    def fused_path(self, features: Optional[torch.Tensor] = None) -> bool:
+        """float32 inference with the node encoder and the edge update in one launch (``routes.encoder_fused``).  Decided from the
+        modules' shapes alone (native 256 widths, LayerNorm, two hidden layers, 17..112 input features), so asking packs no
+        weights."""
+        blk = self.graph_processor.blocks[0]
+        ne, mlp_e, mlp_n = self.node_encoder, blk.edge_model.edge_mlp, blk.node_model.node_mlp
+        if wide.encoder_is_wide(self) or ne.compute_dtype != torch.float32 or mlp_e.compute_dtype != torch.float32:
+            return False
+
+        def form(m):
+            native = not m._layout()[4] and m._norm() is not None and len(m._linears()) == 3
+            return routes.MlpForm(torch.float32, 1 if native else -1, 0 if native else -1, native)
+
+        # (the grad-mode-off first pass of a recomputed training segment counts as training: the two launches give the bits of
+        # the replay the gradients come from; the fused launch sums in another order)
+        train = _autograd_on(self, features) or ag.in_recomputed_first_pass()
+        return routes.encoder_fused(form(ne), ne.native_k(), form(mlp_e), mlp_n.compute_dtype, self.graphs.enc_plan.num_edges,
+                                    self.num_latlons, False, train, bool(blk.deterministic), bool(ops.ENCODER_FUSED))
 
     def team_path(self, features: Optional[torch.Tensor] = None) -> bool:
         """Inference in bf16 with everything the team-pipelined edge kernel needs (see ``AssimilatorDecoder.team_path``).

@@ -49,6 +49,11 @@ EDGE_STREAM = True
 csrc/gw_edge_stream.hip (the segment sums of the batch-shared edge embedding enter the node update as a cached product).
 ``False`` forces the per-edge residual route on ``edge_kernel`` (csrc/gw_edge.hip).  Read on every ``decode``."""
 
+ENCODER_FUSED = True
+"""float32 inference: the encoder's node encoder and edge update run as ONE launch (csrc/gw_encoder_fused.hip) that keeps the
+grid rows in registers and adds no per-edge residual (the segment sums of the batch-shared edge embedding enter the node update
+as a cached product).  ``False`` keeps the two launches (``chain_kernel`` + ``elds_kernel``).  Read on every ``encode``."""
+
 
 def _stream(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
@@ -401,6 +406,30 @@ def edge_update_forward(pm: PackedMLP, batch: int, src: torch.Tensor, dst: torch
                                                      agg.data_ptr(), n_dst, None if save is None else save.c(),
                                                      None if ws is None else ws.data_ptr(), ws_bytes, flags, _stream(agg)),
                    "gw_edge_update_forward")
+    if ev is not None:
+        TIMER.stop(tag, ev, batch)
+
+
+def encoder_fused_forward(pm_node: PackedMLP, pm_edge: PackedMLP, batch: int, src: torch.Tensor, dst: torch.Tensor,
+                          features: Operand, x_dst: Operand, e_in: Operand, e_res: Operand, n_dst: int, agg: torch.Tensor,
+                          tag: Optional[str] = None, save: Optional[SavedActivations] = None, deterministic: bool = False) -> None:
+    """Node encoder (graph_net_block.py:63-77 on ``features[b, src[k]]``) and the encoder's edge update with the scatter_sum of
+    :188 in one launch (include/gw_amd.h: gw_encoder_fused_forward); the encoded rows are never written.  ``agg`` must be zeroed.
+    ``e_res``: fp32 rows of the edge features, or ``ZERO`` (no residual).  ``save`` / ``deterministic``: not implemented by this
+    launch - the library refuses them (there is no fall-back inside: the caller routes such calls to the two launches)."""
+    _require(src, "src", torch.int32)
+    _require(dst, "dst", torch.int32)
+    _require(agg, "agg")
+    n_edges = int(src.shape[0])
+    wn = pm_node.c()
+    we = pm_edge.c((True, False, False))
+    ev = TIMER.start(tag) if TIMER is not None else None
+    with on_device_of(agg):
+        _lib.check(_lib.lib().gw_encoder_fused_forward(batch, n_edges, src.data_ptr(), dst.data_ptr(), features.c(), wn, x_dst.c(),
+                                                       e_in.c(), e_res.c(), we, agg.data_ptr(), n_dst,
+                                                       None if save is None else save.c(),
+                                                       _lib.EDGE_DETERMINISTIC if deterministic else 0, _stream(agg)),
+                   "gw_encoder_fused_forward")
     if ev is not None:
         TIMER.stop(tag, ev, batch)
 

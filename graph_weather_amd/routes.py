@@ -99,6 +99,22 @@ def decoder_stream(edge: MlpForm, node_dtype, n_edges: int, wide: bool, autograd
             and edge.has_norm)
 
 
+def encoder_fused(node_enc: MlpForm, node_enc_k: int, edge: MlpForm, node_dtype, n_edges: int, num_latlons: int, wide: bool,
+                  autograd: bool, deterministic: bool, enabled: bool) -> bool:
+    """The encoder runs its node encoder and its edge update as one launch without residual (csrc/gw_encoder_fused.hip): float32
+    inference in the node encoder (one middle layer, LayerNorm over all 256 features, 17..112 input features: the first layer
+    packed in 28 K-steps) and in both MLPs of the block (as ``decoder_stream``), atomics mode, one edge per grid node
+    (``n_edges == num_latlons``: no grid row is encoded twice) and the switch ``ops.ENCODER_FUSED`` on.  The sums of e then
+    enter the node update as a cached table.  Training, deterministic mode and every other shape keep the two launches."""
+    if not enabled or wide or autograd or deterministic or n_edges <= 0 or n_edges != num_latlons:
+        return False
+    if not (node_enc.dtype == torch.float32 and node_enc.n_mid == 1 and node_enc.ln_width == 0 and node_enc.has_norm
+            and 16 < node_enc_k <= 112):
+        return False
+    return (edge.dtype == torch.float32 and node_dtype == torch.float32 and edge.n_mid == 1 and edge.ln_width == 0
+            and edge.has_norm)
+
+
 # ---- the processor stack ------------------------------------------------------------------------------------------------
 
 

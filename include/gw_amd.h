@@ -309,6 +309,21 @@ int gw_edge_rows_to_tiles(int32_t batch, int32_t n_edges, const float* rows, int
 size_t gw_edge_update_workspace_bytes(int32_t batch, int32_t n_edges, const gw_operand* x_src, const gw_operand* x_dst,
                                       const gw_operand* e_in, const gw_mlp_weights* w, int32_t flags);
 
+/* ---- The fp32 encoder stage in one launch (csrc/gw_encoder_fused.hip; added without a version bump) ------------------
+ *   xg[b, src[k]] = node_encoder(features[b, src[k]])                  (encoder.py:199-205, never written)
+ *   agg[b, dst[k]] += LN(MLP_e(cat[xg[b, src[k]], x_dst[b, dst[k]], e_in[k]])) [+ e_res[k]]
+ * for graphs with one edge per source row in real use (the result does not depend on it: a source row that occurs twice is
+ * encoded twice).  features: raw fp32 rows of 17..112 floats (index NULL, rows_per_batch = grid rows per batch element);
+ * w_node: float32, one middle layer, widths 256, LayerNorm over 256; w_edge as in gw_edge_update_forward with its x_src slice
+ * w1[0] packed, x_dst / e_in projected fp32 rows (one of them may have k == 0); e_res: 256-wide fp32 rows, or k == 0 (no
+ * residual: the caller adds the segment sums of its batch-shared e).  save must be NULL and flags 0 (atomics mode on row
+ * tiles); every other combination returns GW_E_UNSUPPORTED.  With e_res the aggregate is bit for bit the one of
+ * gw_mlp_forward followed by gw_edge_update_forward.  agg must be zeroed. */
+int gw_encoder_fused_forward(int32_t batch, int32_t n_edges, const int32_t* src, const int32_t* dst, const gw_operand* features,
+                             const gw_mlp_weights* w_node, const gw_operand* x_dst, const gw_operand* e_in, const gw_operand* e_res,
+                             const gw_mlp_weights* w_edge, float* agg /* [batch*n_dst,256] */, int32_t n_dst,
+                             const struct gw_activation_save* save /* must be NULL */, int32_t flags /* must be 0 */, void* stream);
+
 /* ---- NodeProcessor.forward after aggregation (graph_net_block.py:189-191) -------------------------------
  *   x_new[b, j] = LN(MLP(cat[x[b, j], agg[b, j]])) + x_res[b, j]
  * x may be raw, pre-projected or zeros (k == 0: the decoder's lat/lon rows are zeros, assimilator_decoder.py:84,
