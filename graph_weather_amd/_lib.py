@@ -48,6 +48,9 @@ EXPORTS = [
     "gw_gemm_tn_ordered_workspace_bytes", "gw_gemm_tn_ordered", "gw_layernorm_backward_ordered_workspace_bytes",
     "gw_layernorm_backward_ordered",
     "gw_encoder_fused_forward",
+    "gw_graph_attention_forward", "gw_graph_attention_backward", "gw_cond_layernorm_forward", "gw_cond_layernorm_backward",
+    "gw_beta_gate_forward", "gw_beta_gate_workspace_bytes", "gw_beta_gate_backward", "gw_silu_forward", "gw_silu_backward",
+    "gw_fourier_forward", "gw_fourier_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -82,6 +85,8 @@ class GwConstraintArgs(Structure):  # include/gw_amd.h: gw_constraint_args
                 ("hr", c_void_p), ("ld_hr", c_int32), ("lr", c_void_p), ("ld_lr", c_int32), ("map", c_void_p),
                 ("inv_ptr", c_void_p), ("inv_idx", c_void_p)]
 
+
+ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2  # GW_ACT_*
 
 THERMAL_MAX_TAPS = 7  # GW_THERMAL_MAX_TAPS
 THERMAL_A_PLAIN, THERMAL_A_GN_RELU, THERMAL_A_DIFFUSE = 0, 1, 2  # GW_THERMAL_A_*
@@ -404,6 +409,32 @@ def lib():
     L.gw_layernorm_backward_ordered.restype = c_int
     L.gw_layernorm_backward_ordered.argtypes = [c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
                                                 c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
+    L.gw_graph_attention_forward.restype = c_int
+    L.gw_graph_attention_forward.argtypes = [c_int32] * 5 + [c_void_p, c_void_p, c_void_p] + [c_void_p, c_int32] * 4 + [
+        c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p]
+    L.gw_graph_attention_backward.restype = c_int
+    L.gw_graph_attention_backward.argtypes = [c_int32] * 5 + [c_void_p] * 6 + [c_void_p, c_int32] * 4 + [
+        c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p] + [c_void_p, c_int32] * 4 + [c_void_p]
+    L.gw_cond_layernorm_forward.restype = c_int
+    L.gw_cond_layernorm_forward.argtypes = [c_int64, c_int32, c_int32] + [c_void_p, c_int32] * 4 + [c_void_p]
+    L.gw_cond_layernorm_backward.restype = c_int
+    L.gw_cond_layernorm_backward.argtypes = [c_int64, c_int32, c_int32] + [c_void_p, c_int32] * 5 + [c_void_p, c_void_p, c_int32, c_void_p]
+    L.gw_beta_gate_forward.restype = c_int
+    L.gw_beta_gate_forward.argtypes = [c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p,
+                                       c_void_p]
+    L.gw_beta_gate_workspace_bytes.restype = c_size_t
+    L.gw_beta_gate_workspace_bytes.argtypes = [c_int64, c_int32]
+    L.gw_beta_gate_backward.restype = c_int
+    L.gw_beta_gate_backward.argtypes = [c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                        c_void_p, c_size_t, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
+    L.gw_silu_forward.restype = c_int
+    L.gw_silu_forward.argtypes = [c_int64, c_void_p, c_void_p, c_void_p]
+    L.gw_silu_backward.restype = c_int
+    L.gw_silu_backward.argtypes = [c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_fourier_forward.restype = c_int
+    L.gw_fourier_forward.argtypes = [c_int64, c_int32, c_float, c_void_p, c_void_p, c_int32, c_void_p]
+    L.gw_fourier_backward.restype = c_int
+    L.gw_fourier_backward.argtypes = [c_int64, c_int32, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

@@ -808,6 +808,70 @@ int gw_conv3d_backward(int32_t batch, int32_t cin, int32_t cout, int32_t d, int3
                        const int64_t* stride_x, const float* weight, const float* dout, const int64_t* stride_dout, void* workspace,
                        size_t workspace_bytes, float* dx, const int64_t* stride_dx, float* dweight, float* dbias, void* stream);
 
+/* =====================================================================================================================
+ * GenCast layers (graph_weather/models/gencast/layers), csrc/gw_gencast.hip: graph-transformer attention (the TransformerConv
+ * of the mesh processor) and the row operations around it.  All fp32, no atomics, every sum in one fixed order (bitwise
+ * reproducible), no host synchronisation; a launch over 0 rows or 0 edges returns GW_OK without launching (the caller zero-fills
+ * what such a launch would have written).
+ *
+ * Graph attention over a destination-sorted CSR (GraphPlan): the edges [dst_ptr[i], dst_ptr[i + 1]) end in destination row i,
+ * sorted edge t starts in source row src[t] and is the caller's edge perm[t] (perm NULL: t).  Per head h of `heads`, with
+ * C = dim_head >= 1 and heads * C <= 4096 (GW_E_UNSUPPORTED above):
+ *   s_t = q[i, h] . (k[src[t], h] + e[perm[t], h]) / sqrt(C),  alpha = softmax of s over the edges of i,
+ *   out[i, h] = sum_t alpha_t (v[src[t], h] + e[perm[t], h]);  a destination without edges gets 0.
+ * q [n_dst, heads C] is read from the destination table, k and v [n_src, heads C] from the source table, each with its own
+ * leading dimension (column blocks of one stacked projection are read in place); e [n_edges, heads C] (may be NULL) is read in
+ * the caller's edge order.  mean 0: out [n_dst, heads C] holds the heads side by side; mean 1: out [n_dst, C] is their mean and
+ * out_heads [n_dst, heads C] (may be NULL in inference) receives the per-head rows the backward needs.  lse [2, n_dst * heads]:
+ * plane 0 the maximum of the scores of (i, h), plane 1 log sum_t exp(s_t - max) - two planes for the reason given at
+ * gw_attention_forward; both 0 for a destination without edges.  The softmax is online: nothing of size E x heads x C or
+ * E x heads is written.  dim_head and every leading dimension a multiple of 4 with 16-byte aligned tables: 16-byte loads;
+ * anything else runs a scalar path.  One wave walks one destination's edges: any degree is correct, near-uniform degrees are fast.
+ *
+ * gw_graph_attention_backward recomputes the probabilities from q, k, e and lse.  out_heads: the per-head forward rows (mean 0:
+ * out itself); dout [n_dst, heads C] (mean 1: [n_dst, C]).  One launch over destinations writes delta [n_dst * heads] (scratch
+ * the caller provides) = rowsum(dout_h o out_h), dq and - with e - de [n_edges, heads C] in the caller's edge order (de NULL:
+ * not wanted); one launch over sources walks src_pos / src_ptr (GraphPlan.src_sorted: sorted positions grouped by source row;
+ * dst[t] = destination row of sorted edge t) and writes dk and dv.  Every row of dq, dk, dv, de is written. */
+int gw_graph_attention_forward(int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads, int32_t dim_head, const int32_t* dst_ptr,
+                               const int32_t* src, const int64_t* perm, const float* q, int32_t ld_q, const float* k, int32_t ld_k,
+                               const float* v, int32_t ld_v, const float* e, int32_t ld_e, int32_t mean, float* out, int32_t ld_out,
+                               float* out_heads, int32_t ld_out_heads, float* lse, void* stream);
+int gw_graph_attention_backward(int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads, int32_t dim_head, const int32_t* dst_ptr,
+                                const int32_t* src, const int32_t* dst, const int64_t* perm, const int32_t* src_pos,
+                                const int32_t* src_ptr, const float* q, int32_t ld_q, const float* k, int32_t ld_k, const float* v,
+                                int32_t ld_v, const float* e, int32_t ld_e, int32_t mean, const float* out_heads, int32_t ld_out_heads,
+                                const float* dout, int32_t ld_dout, const float* lse, float* delta, float* dq, int32_t ld_dq, float* dk,
+                                int32_t ld_dk, float* dv, int32_t ld_dv, float* de, int32_t ld_de, void* stream);
+/* ConditionalLayerNorm (modules.py): out[r] = act(scale[r] o LN(x[r]) + bias[r]) with LN = LayerNorm without affine, eps 1e-5, and
+ * scale, bias one row per row of x; act = GW_ACT_*.  Backward: dx, dscale, dbias (each may be NULL; dscale and dbias share ld_dsb). */
+#define GW_ACT_NONE 0
+#define GW_ACT_RELU 1
+#define GW_ACT_SILU 2
+int gw_cond_layernorm_forward(int64_t rows, int32_t width, int32_t act, const float* x, int32_t ld_x, const float* scale, int32_t ld_scale,
+                              const float* bias, int32_t ld_bias, float* out, int32_t ld_out, void* stream);
+int gw_cond_layernorm_backward(int64_t rows, int32_t width, int32_t act, const float* x, int32_t ld_x, const float* scale,
+                               int32_t ld_scale, const float* bias, int32_t ld_bias, const float* dout, int32_t ld_dout, float* dx,
+                               int32_t ld_dx, float* dscale, float* dbias, int32_t ld_dsb, void* stream);
+/* TransformerConv's beta gate: g[r] = sigmoid(w_a . out[r] + w_b . x_r[r] + w_c . (out[r] - x_r[r])), w = [w_a | w_b | w_c]
+ * (lin_beta.weight, 3 width floats), y[r] = g x_r[r] + (1 - g) out[r]; gate [rows] keeps g for the backward.  Backward: d_out and
+ * d_xr (each may be NULL, leading dimension ld_d) and dw [3 width], formed as partials per slab of 256 rows in
+ * gw_beta_gate_workspace_bytes (host-side query; 0 with the error set on bad arguments) of scratch, added in slab order. */
+int gw_beta_gate_forward(int64_t rows, int32_t width, const float* out, int32_t ld_out, const float* x_r, int32_t ld_xr, const float* w,
+                         float* y, int32_t ld_y, float* gate, void* stream);
+size_t gw_beta_gate_workspace_bytes(int64_t rows, int32_t width);
+int gw_beta_gate_backward(int64_t rows, int32_t width, const float* out, int32_t ld_out, const float* x_r, int32_t ld_xr, const float* w,
+                          const float* gate, const float* dy, int32_t ld_dy, void* workspace, size_t workspace_bytes, float* d_out,
+                          float* d_xr, int32_t ld_d, float* dw, void* stream);
+/* y = x sigmoid(x) on n dense floats; dx = dy sigmoid(x) (1 + x (1 - sigmoid(x))). */
+int gw_silu_forward(int64_t n, const float* x, float* y, void* stream);
+int gw_silu_backward(int64_t n, const float* x, const float* dy, float* dx, void* stream);
+/* FourierEmbedding.fourier_features (modules.py): out[r, i] = cos(t[r] f_i), out[r, F + i] = sin(t[r] f_i) for i < F =
+ * num_frequencies, f_i = exp(-ln(base_period) i / F) formed in float32, accurate cosf / sinf.  Backward: dt[r]. */
+int gw_fourier_forward(int64_t rows, int32_t num_frequencies, float base_period, const float* t, float* out, int32_t ld_out, void* stream);
+int gw_fourier_backward(int64_t rows, int32_t num_frequencies, float base_period, const float* t, const float* dout, int32_t ld_dout,
+                        float* dt, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
