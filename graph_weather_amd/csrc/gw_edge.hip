@@ -96,27 +96,10 @@ __device__ __forceinline__ const float* chunk_src(const EdgeArgs& a, int i) {
 template <bool RAW, int NPROJ>
 __global__ __launch_bounds__(kThreads, 2) void edge_kernel(const EdgeArgs a) {
   float* const lds = lds_base();
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int j = lane & 15;
-  const int q = lane >> 4;
-  int tile = blockIdx.x;
-  if (a.xcd_base > 0) {
-    const int xcd = tile & 7, idx = tile >> 3;
-    tile = xcd * a.xcd_base + (xcd < a.xcd_rem ? xcd : a.xcd_rem) + idx;
-  }
-  const int tile_c0 = tile * kColsPerWG;
-  const int c_raw = tile_c0 + wave * kColsPerWave + j;
-  const bool valid = c_raw < a.n_cols;
-  const int c = valid ? c_raw : a.n_cols - 1;
-  const int b = c / a.n_edges;
-  const int k = c - b * a.n_edges;
-  const int total = kChunksPerLayer * ((RAW ? 1 : 0) + a.n_mid + 1);  // weight chunks per tile
-
-  // anti-phase start of the second batch of workgroups (see chain_kernel)
-  if (a.stagger > 0 && (blockIdx.x >> 8) == 1) {
-    for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  }
+  GW_TILE_COORDS(a.n_cols, a.n_edges, a.xcd_base, a.xcd_rem)
+  // weight chunks per tile.  (Unused, and kept: without this line edge_kernel<true, 2> compiles to another schedule.)
+  const int total = kChunksPerLayer * ((RAW ? 1 : 0) + a.n_mid + 1);
+  stagger_start(a.stagger);
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   GW_STAMP(0)
 
@@ -141,12 +124,9 @@ __global__ __launch_bounds__(kThreads, 2) void edge_kernel(const EdgeArgs a) {
   constexpr int NR = RAW ? NPROJ : NPROJ + 1;
   const float* brow = a.b1 + 4 * q;
   f32x4 ring[2][NR][2];
-#define GW_REQUEST_SLICE(slot, slice)                                          \
+#define GW_REQUEST_SLICE_B(slot, slice)                                        \
   {                                                                            \
-    _Pragma("unroll") for (int p = 0; p < NPROJ; ++p) {                        \
-      ring[slot][p][0] = hld4<128 * (slice)>(prow[p]);                         \
-      ring[slot][p][1] = hld4<128 * (slice) + 64>(prow[p]);                    \
-    }                                                                          \
+    GW_REQUEST_SLICE(slot, slice)                                              \
     if (!RAW) {                                                                \
       ring[slot][NR - 1][0] = hld4<128 * (slice)>(brow);                       \
       ring[slot][NR - 1][1] = hld4<128 * (slice) + 64>(brow);                  \
@@ -207,8 +187,8 @@ __global__ __launch_bounds__(kThreads, 2) void edge_kernel(const EdgeArgs a) {
 #pragma unroll
       for (int i = 0; i < 8; ++i) in8[i] = x[8 * cc + i];
       if (cc == kChunksPerLayer - 3) {  // the first two ring slices, once most of x is dead
-        GW_REQUEST_SLICE(0, 0)
-        GW_REQUEST_SLICE(1, 1)
+        GW_REQUEST_SLICE_B(0, 0)
+        GW_REQUEST_SLICE_B(1, 1)
       }
       if (cc == kChunksPerLayer - 1) hld_row(acc2, a.b_mid + 4 * q);  // next layer's bias, under the last chunk (x is dead)
       if (cc == kChunksPerLayer - 1) {
@@ -220,11 +200,11 @@ __global__ __launch_bounds__(kThreads, 2) void edge_kernel(const EdgeArgs a) {
     wait_regs<0>(ring[0]);  // (landed long ago: everything was drained by the vmcnt(0) boundaries above)
     wait_regs<0>(ring[1]);
     GW_CONSUME_SLICE(0, 0)
-    GW_REQUEST_SLICE(0, 2)
+    GW_REQUEST_SLICE_B(0, 2)
   } else {
     hld_row(acc2, a.b_mid + 4 * q);
-    GW_REQUEST_SLICE(0, 0)
-    GW_REQUEST_SLICE(1, 1)
+    GW_REQUEST_SLICE_B(0, 0)
+    GW_REQUEST_SLICE_B(1, 1)
     wait_regs<2 * NR>(acc2);     // chunk 0, the bias rows and slice 0 have landed;
     wait_regs<2 * NR>(ring[0]);  // slice 1 stays in flight
     lds_barrier();
@@ -232,7 +212,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_kernel(const EdgeArgs a) {
 #pragma unroll
     for (int b4 = 0; b4 < 4; ++b4) a_cur[b4] = *(const f32x4*)(lds + lane * 4 + b4 * 256);
     GW_CONSUME_SLICE(0, 0)
-    GW_REQUEST_SLICE(0, 2)
+    GW_REQUEST_SLICE_B(0, 2)
   }
   GW_STAMP(2)
 
@@ -249,15 +229,15 @@ __global__ __launch_bounds__(kThreads, 2) void edge_kernel(const EdgeArgs a) {
     if ((cc) + 1 < kChunksPerLayer) GW_CONSUME_SLICE(((cc) + 1) & 1, (cc) + 1)             \
   }
   GW_PRODUCE_CHUNK(0)
-  GW_REQUEST_SLICE(1, 3)
+  GW_REQUEST_SLICE_B(1, 3)
   GW_PRODUCE_CHUNK(1)
-  GW_REQUEST_SLICE(0, 4)
+  GW_REQUEST_SLICE_B(0, 4)
   GW_PRODUCE_CHUNK(2)
-  GW_REQUEST_SLICE(1, 5)
+  GW_REQUEST_SLICE_B(1, 5)
   GW_PRODUCE_CHUNK(3)
-  GW_REQUEST_SLICE(0, 6)
+  GW_REQUEST_SLICE_B(0, 6)
   GW_PRODUCE_CHUNK(4)
-  GW_REQUEST_SLICE(1, 7)
+  GW_REQUEST_SLICE_B(1, 7)
   GW_PRODUCE_CHUNK(5)
   GW_PRODUCE_CHUNK(6)
   GW_PRODUCE_CHUNK(7)
@@ -322,57 +302,14 @@ __global__ __launch_bounds__(kThreads, 2) void edge_kernel(const EdgeArgs a) {
 #pragma unroll
       for (int t = 0; t < 16; ++t) stg4(sr + 16 * t, o[t]);
     }
-    constexpr float inv_n = 1.0f / 256.0f;
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) s += (o[t].x + o[t].y) + (o[t].z + o[t].w);
-    s += __shfl_xor(s, 16);
-    s += __shfl_xor(s, 32);
-    const float mean = s * inv_n;
-    float v = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = o[t][r] - mean;
-        v += d * d;
-      }
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    const float rstd = 1.0f / sqrtf(v * inv_n + 1e-5f);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const f32x4 gm = ldg4(a.gamma + 16 * t + 4 * q);
-      const f32x4 bt = ldg4(a.beta + 16 * t + 4 * q);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[t][r] = (o[t][r] - mean) * rstd * gm[r] + bt[r] + rres[t][r];
-    }
+    GW_LAYERNORM256(o, ldg4, a.gamma, a.beta, + rres[t][r])
   }
 
   if (GW_SKIP(a) >= 2) return;
-  // ---- stage e' through LDS: [64 columns][260] + 64 global destination ids ----
-  __syncthreads();  // every wave is done reading the weight buffers
-  {
-    float* srow = lds + (wave * kColsPerWave + j) * kStageLd + 4 * q;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) *(f32x4*)(srow + 16 * t) = o[t];
-    if (q == 0) ((int*)(lds + kStageFloats))[wave * kColsPerWave + j] = gd_id;
-  }
-  __syncthreads();
+  // ---- stage e' through LDS, e_out rows ----
+  GW_STAGE_ROWS(o, gd_id)
   GW_STAMP(5)
-  const int* gdl = (const int*)(lds + kStageFloats);
-
-  // e_out rows: one 1 KiB coalesced store per row (wave w writes the rows of its own 16 columns)
-  if (a.e_out != nullptr) {
-#pragma unroll 4
-    for (int i = 0; i < kColsPerWave; ++i) {
-      const int col = wave * kColsPerWave + i;
-      if (tile_c0 + col < a.n_cols) {
-        const f32x4 vv = *(const f32x4*)(lds + col * kStageLd + 4 * lane);
-        stg4(a.e_out + (size_t)(tile_c0 + col) * 256 + 4 * lane, vv);
-      }
-    }
-  }
+  if (a.e_out != nullptr) store_e_rows(lds, a.e_out, tile_c0, a.n_cols, wave, lane);
 
   if (GW_SKIP(a) >= 1) return;
   // segment sum: thread f owns feature f; columns are sorted by global destination id, so equal ids form runs.
@@ -446,7 +383,7 @@ __global__ __launch_bounds__(kThreads, 2) void edge_kernel(const EdgeArgs a) {
       }
     }
   }
-#undef GW_REQUEST_SLICE
+#undef GW_REQUEST_SLICE_B
 #undef GW_CONSUME_SLICE
 #undef GW_PRODUCE_CHUNK
 
@@ -465,12 +402,8 @@ __global__ __launch_bounds__(kThreads, 2) void edge_kernel(const EdgeArgs a) {
 
 template <typename K>
 int launch(K kernel, const EdgeArgs& a, void* stream) {
-  static DeviceOnce once;  // per template instantiation and device
   static const int lds_bytes = kEdgeLdsBytes + GW_TUNE("GW_EDGE_LDS_PAD", 0);  // tuning aid: > 15 KiB of padding forces one workgroup per CU
-  if (once.first()) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-  const int grid = (a.n_cols + kColsPerWG - 1) / kColsPerWG;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds_bytes, (hipStream_t)stream, a);
-  return check_launch("edge_kernel launch");
+  return launch_tile_kernel(kernel, a, lds_bytes, "edge_kernel launch", stream);
 }
 
 inline bool is_raw(const gw_operand* op) { return op->k > 0 && !op->projected; }
@@ -577,34 +510,15 @@ int edge_fast_launch(int32_t batch, int32_t n_edges, const int32_t* src, const i
     a.dbg = g_dbg;
     a.dbg_cap = g_dbg_cap;
   }
-  {
-    static int skip = -1;
-    if (skip < 0) skip = GW_TUNE("GW_EDGE_SKIP", 0);
-    a.skip = skip;
-    static const int dma6 = GW_TUNE("GW_EDGE_DMA6", 0);
-    a.dma6 = dma6;
-  }
-  {
-    static int stagger_override = -2;
-    if (stagger_override == -2) stagger_override = GW_TUNE("GW_STAGGER", -1);
-    const int passes = 1 + a.n_mid + (raw ? 1 : 0);
-    a.stagger = stagger_override >= 0 ? stagger_override * passes : 2 * passes + 2;
-    if ((a.n_cols + kColsPerWG - 1) / kColsPerWG <= 256) a.stagger = 0;
-  }
-  {
-    static int xcd_map = -1;  // GW_XCD_MAP=0: workgroup i takes tile i (A/B measurements)
-    if (xcd_map < 0) xcd_map = GW_TUNE("GW_XCD_MAP", 1);
-    const int tiles = (a.n_cols + kColsPerWG - 1) / kColsPerWG;
-    a.xcd_base = (xcd_map != 0 && tiles >= 64) ? tiles / 8 : 0;
-    a.xcd_rem = tiles % 8;
-  }
+  const int tiles = (a.n_cols + kColsPerWG - 1) / kColsPerWG;
+  fill_tile_schedule(a, tiles, 1 + a.n_mid + (raw ? 1 : 0));  // (every GW_EDGE_SKIP value applies here)
   int rc;
   if (raw) rc = n_proj == 1 ? launch(edge_kernel<true, 1>, a, stream) : launch(edge_kernel<true, 2>, a, stream);
   else if (n_proj == 1) rc = launch(edge_kernel<false, 1>, a, stream);
   else if (n_proj == 2) rc = launch(edge_kernel<false, 2>, a, stream);
   else rc = launch(edge_kernel<false, 3>, a, stream);
   if (rc != GW_OK || carry == nullptr) return rc;
-  return segment_fixup_launch((a.n_cols + kColsPerWG - 1) / kColsPerWG, carry, agg, stream);
+  return segment_fixup_launch(tiles, carry, agg, stream);
 }
 
 }  // namespace gw

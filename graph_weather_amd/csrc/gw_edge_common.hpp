@@ -1,6 +1,11 @@
-// gw_edge_common.hpp - device helpers shared by the hand-scheduled fp32 edge-update kernels (gw_edge.hip: edge_kernel,
-// gw_edge_stream.hip: its persistent decoder form): loads hipcc must not count and their counted waits, the LDS weight ring
-// (asm-issued LDS-DMA pieces, the LDS-only barrier) and the chunk macro with the hand-over in front of a chunk's last MFMAs.
+// gw_edge_common.hpp - what the hand-scheduled fp32 edge-update kernels share (gw_edge.hip: edge_kernel, gw_edge_lds.hip: its
+// inference form with the constants in LDS, gw_edge_stream.hip: the decoder form without residual, gw_encoder_fused.hip: node
+// encoder + edge update in one launch; one workgroup per 64-column tile in all four).  Device side: loads hipcc must not count
+// and their counted waits, the LDS weight ring (asm-issued LDS-DMA pieces, the LDS-only barrier), the chunk macro with the
+// hand-over in front of a chunk's last MFMAs, and the tile code around the matrix passes - tile coordinates, constants in LDS,
+// LayerNorm, staging, e' store, segment sum.  Host side: the launch and the tile schedule.  Whether a shared piece is a function
+// or a macro was decided by the generated code: a function where the kernels compile to the same
+// instructions as with the text in place, a macro where inlining changed the floating-point contraction.
 #ifndef GW_EDGE_COMMON_HPP
 #define GW_EDGE_COMMON_HPP
 
@@ -178,6 +183,191 @@ __device__ __forceinline__ void issue_pieces(const float* __restrict__ g, int bu
     }                                                                                                          \
     ++ci;                                                                                                      \
   }
+
+// GW_REQUEST_SLICE(slot, slice): request slice `slice` (features 32 slice + 16 h + 4q .. +3, h = 0, 1) of the NPROJ projected
+// operands' rows prow[p] into ring[slot][p][h].  Expected in scope: NPROJ, prow, ring.
+#define GW_REQUEST_SLICE(slot, slice)                                          \
+  {                                                                            \
+    _Pragma("unroll") for (int p = 0; p < NPROJ; ++p) {                        \
+      ring[slot][p][0] = hld4<128 * (slice)>(prow[p]);                         \
+      ring[slot][p][1] = hld4<128 * (slice) + 64>(prow[p]);                    \
+    }                                                                          \
+  }
+
+// ---- the tile around the matrix passes --------------------------------------------------------------------------
+// Where a thread works: workgroup -> tile (XCD-aware order, see EdgeArgs), lane (j, q) of wave `wave` -> column c = edge k of
+// sample b; columns past the end (valid == false) compute on the last column and store nothing.
+// GW_TILE_COORDS declares lane, wave, j, q, tile, tile_c0, valid, c, b, k in the kernel's scope.  A macro: returned from a
+// function (a struct of the ten values) the same text compiled to other code in the kernels' epilogues.
+#define GW_TILE_COORDS(N_COLS, N_EDGES, XCD_BASE, XCD_REM)                                \
+  const int lane = threadIdx.x & 63;                                                      \
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                      \
+  const int j = lane & 15;                                                                \
+  const int q = lane >> 4;                                                                \
+  int tile = blockIdx.x;                                                                  \
+  if ((XCD_BASE) > 0) {                                                                   \
+    const int xcd = tile & 7, idx = tile >> 3;                                            \
+    tile = xcd * (XCD_BASE) + (xcd < (XCD_REM) ? xcd : (XCD_REM)) + idx;                  \
+  }                                                                                       \
+  const int tile_c0 = tile * kColsPerWG;                                                  \
+  const int c_raw = tile_c0 + wave * kColsPerWave + j;                                    \
+  const bool valid = c_raw < (N_COLS);                                                    \
+  const int c = valid ? c_raw : (N_COLS) - 1;                                             \
+  const int b = c / (N_EDGES);                                                            \
+  const int k = c - b * (N_EDGES);
+
+// anti-phase start of the second batch of workgroups (see chain_kernel)
+__device__ __forceinline__ void stagger_start(int stagger) {
+  if (stagger > 0 && (blockIdx.x >> 8) == 1) {
+    for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(127);
+  }
+}
+
+// ---- constants in LDS: an MLP's b1 | b_mid | b_out | gamma | beta as one set of 5 x 256 floats behind the staging area and
+// the destination ids.  Thread f carries feature f of each vector there; the kernels' prologues differ in how the five values
+// are requested and waited for, so that part stays with them.
+constexpr int kConstSetFloats = 5 * 256;
+constexpr int kConstOff = kStageFloats + kColsPerWG;
+static_assert((kConstOff * 4) % 16 == 0, "constants are read as 16-byte vectors");
+constexpr int kB1 = 0, kBMid = 256, kBOut = 512, kGamma = 768, kBeta = 1024;  // float offsets inside a set
+// one float per thread of a constant vector, requested like the indices (a load hipcc does not count)
+__device__ __forceinline__ float hld1(const float* p) {
+  float v;
+  asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p) : "memory");
+  return v;
+}
+// cv[0..4] -> set `set` (float offset behind kConstOff); visible to the workgroup after the next lds_barrier()
+__device__ __forceinline__ void consts_to_lds(float* lds, int set, const float* cv) {
+  float* cw = lds + kConstOff + threadIdx.x;
+  cw[set + kB1] = cv[0];
+  cw[set + kBMid] = cv[1];
+  cw[set + kBOut] = cv[2];
+  cw[set + kGamma] = cv[3];
+  cw[set + kBeta] = cv[4];
+}
+
+// GW_LAYERNORM256(O, LD4, GAMMA, BETA, RES): LayerNorm over the 256 features of each column (eps 1e-5, biased variance) of the
+// accumulator tiles O[16] (the caller has added the bias).  gamma / beta vectors of tile t are LD4(GAMMA + 16 * t + 4 * q) with
+// LD4 = GW_LDS4 (constants in LDS) or ldg4 (global memory); RES is empty or a residual addend in the macro's indices t, r
+// (`+ rres[t][r]`).  Expected in scope: q.  A macro, not a function: as an inlined function hipcc no longer contracts
+// v += d * d (and others) into fused multiply-adds, which changes the rounding.
+#define GW_LDS4(p) (*(const f32x4*)(p))
+#define GW_LAYERNORM256(O, LD4, GAMMA, BETA, RES)                                                              \
+  {                                                                                                            \
+    constexpr float inv_n = 1.0f / 256.0f;                                                                     \
+    float s = 0.f;                                                                                             \
+    _Pragma("unroll") for (int t = 0; t < 16; ++t) s += (O[t].x + O[t].y) + (O[t].z + O[t].w);                 \
+    s += __shfl_xor(s, 16);                                                                                    \
+    s += __shfl_xor(s, 32);                                                                                    \
+    const float mean = s * inv_n;                                                                              \
+    float v = 0.f;                                                                                             \
+    _Pragma("unroll") for (int t = 0; t < 16; ++t) _Pragma("unroll") for (int r = 0; r < 4; ++r) {             \
+      const float d = O[t][r] - mean;                                                                          \
+      v += d * d;                                                                                              \
+    }                                                                                                          \
+    v += __shfl_xor(v, 16);                                                                                    \
+    v += __shfl_xor(v, 32);                                                                                    \
+    const float rstd = 1.0f / sqrtf(v * inv_n + 1e-5f);                                                        \
+    _Pragma("unroll") for (int t = 0; t < 16; ++t) {                                                           \
+      const f32x4 gm = LD4(GAMMA + 16 * t + 4 * q);                                                            \
+      const f32x4 bt = LD4(BETA + 16 * t + 4 * q);                                                             \
+      _Pragma("unroll") for (int r = 0; r < 4; ++r) O[t][r] = (O[t][r] - mean) * rstd * gm[r] + bt[r] RES;     \
+    }                                                                                                          \
+  }
+
+// GW_STAGE_ROWS(O, GD_ID): stage the rows O[16] through LDS: [64 columns][kStageLd] floats over the weight buffers + the 64 global
+// destination ids behind them (GD_ID: -1 for a column past the end); declares gdl, the ids.  Expected in scope: lds, wave, j, q.
+// A macro: as a function edge_kernel recomputed 4 * q for the row address instead of reusing the prologue's register.
+#define GW_STAGE_ROWS(O, GD_ID)                                                                                \
+  __syncthreads(); /* every wave is done reading the weight buffers */                                         \
+  {                                                                                                            \
+    float* srow = lds + (wave * kColsPerWave + j) * kStageLd + 4 * q;                                          \
+    _Pragma("unroll") for (int t = 0; t < 16; ++t) *(f32x4*)(srow + 16 * t) = O[t];                            \
+    if (q == 0) ((int*)(lds + kStageFloats))[wave * kColsPerWave + j] = (GD_ID);                               \
+  }                                                                                                            \
+  __syncthreads();                                                                                             \
+  const int* gdl = (const int*)(lds + kStageFloats);
+
+// e_out rows from the staged tile: one 1 KiB coalesced store per row (wave w writes the rows of its own 16 columns)
+__device__ __forceinline__ void store_e_rows(const float* lds, float* e_out, int tile_c0, int n_cols, int wave, int lane) {
+#pragma unroll 4
+  for (int i = 0; i < kColsPerWave; ++i) {
+    const int col = wave * kColsPerWave + i;
+    if (tile_c0 + col < n_cols) {
+      const f32x4 vv = *(const f32x4*)(lds + col * kStageLd + 4 * lane);
+      stg4(e_out + (size_t)(tile_c0 + col) * 256 + 4 * lane, vv);
+    }
+  }
+}
+
+// GW_SEGMENT_SUM_ATOMICS(AGG): segment sum of the staged tile in atomics mode.  Thread f owns feature f; columns are sorted by
+// global destination id (gdl, from GW_STAGE_ROWS), so equal ids form runs.  Interior runs belong to this tile alone -> plain
+// stores; the first and the last run may continue in the neighbouring tiles -> atomics (AGG is zero-filled by the caller).  See
+// edge_kernel for the ballot walk; its own copy also has the deterministic mode.  Expected in scope: lds, gdl, lane.  A macro:
+// as a function the walk compiled to other code (more s_waitcnt in estream_kernel<2>, another instruction order in <1>).
+#define GW_SEGMENT_SUM_ATOMICS(AGG)                                                                            \
+  {                                                                                                            \
+    const int f = threadIdx.x;                                                                                 \
+    float vv[kColsPerWG];                                                                                      \
+    _Pragma("unroll") for (int i = 0; i < kColsPerWG; ++i) vv[i] = lds[i * kStageLd + f];                      \
+    const int gdv = gdl[lane];                                                                                 \
+    const int gdn = gdl[lane < kColsPerWG - 1 ? lane + 1 : lane];                                              \
+    const unsigned long long ends = __ballot(lane == kColsPerWG - 1 || gdn != gdv); /* bit i: a run ends with column i */ \
+    float run = 0.f;                                                                                           \
+    bool first = true;                                                                                         \
+    _Pragma("unroll") for (int i = 0; i < kColsPerWG; ++i) {                                                   \
+      run += vv[i];                                                                                            \
+      if (__builtin_expect((ends >> i) & 1ull, 0)) {                                                           \
+        const int cur = __builtin_amdgcn_readlane(gdv, i);                                                     \
+        if (cur >= 0) {                                                                                        \
+          float* dstp = (AGG) + (size_t)cur * 256 + f;                                                         \
+          if (first || i == kColsPerWG - 1) {                                                                  \
+            __hip_atomic_fetch_add((GW_AS1 float*)dstp, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      \
+          } else {                                                                                             \
+            stg1(dstp, run);                                                                                   \
+          }                                                                                                    \
+        }                                                                                                      \
+        first = false;                                                                                         \
+        run = 0.f;                                                                                             \
+      }                                                                                                        \
+    }                                                                                                          \
+  }
+
+// ---- host side -----------------------------------------------------------------------------------------------
+// One workgroup per 64-column tile.  (K is the same type for every instantiation of a kernel template, so the dynamic-LDS
+// limit is raised once per args struct and device, for the instantiation launched first.)
+template <typename K, typename A>
+int launch_tile_kernel(K kernel, const A& a, int lds_bytes, const char* name, void* stream) {
+  static DeviceOnce once;
+  if (once.first()) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  const int grid = (a.n_cols + kColsPerWG - 1) / kColsPerWG;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds_bytes, (hipStream_t)stream, a);
+  return check_launch(name);
+}
+
+// the tuning switches GW_CHUNK reads; args without them (EncfArgs: GW_FCHUNK has no switches) take the second overload
+template <typename A>
+auto fill_chunk_switches(A& a, int) -> decltype((void)a.skip) {
+  static const int skip = GW_TUNE("GW_EDGE_SKIP", 0);
+  static const int dma6 = GW_TUNE("GW_EDGE_DMA6", 0);
+  a.skip = skip;
+  a.dma6 = dma6;
+}
+template <typename A>
+void fill_chunk_switches(A&, long) {}
+
+// Start-up stagger, XCD-aware tile order (see EdgeArgs) and the chunk switches of a launch of `tiles` tiles whose kernel makes
+// `passes` passes over 256 x 256 weights per tile.
+template <typename A>
+void fill_tile_schedule(A& a, int tiles, int passes) {
+  fill_chunk_switches(a, 0);
+  static const int stagger_override = GW_TUNE("GW_STAGGER", -1);
+  a.stagger = stagger_override >= 0 ? stagger_override * passes : 2 * passes + 2;
+  if (tiles <= 256) a.stagger = 0;
+  static const int xcd_map = GW_TUNE("GW_XCD_MAP", 1);  // 0: workgroup i takes tile i (A/B measurements)
+  a.xcd_base = (xcd_map != 0 && tiles >= 64) ? tiles / 8 : 0;
+  a.xcd_rem = tiles % 8;
+}
 
 }  // namespace
 

@@ -27,13 +27,9 @@ using namespace gw;
 
 namespace {
 
-constexpr int kConstFloats = 5 * 256;                          // b1 | b_mid | b_out | gamma | beta
-constexpr int kConstOff = kStageFloats + kColsPerWG;           // behind the staging area and the 64 destination ids
-constexpr int kEldsLdsBytes = (kConstOff + kConstFloats) * 4;
-static_assert(kEldsLdsBytes == 71936, "staging + destination ids + constants");
-static_assert((kConstOff * 4) % 16 == 0, "constants are read as 16-byte vectors");
+constexpr int kEldsLdsBytes = (kConstOff + kConstSetFloats) * 4;
+static_assert(kEldsLdsBytes == 71936, "staging + destination ids + one set of constants");
 static_assert(2 * kEldsLdsBytes <= 160 * 1024, "two workgroups per CU must fit the 160 KiB of LDS");
-constexpr int kB1 = 0, kBMid = 256, kBOut = 512, kGamma = 768, kBeta = 1024;  // float offsets behind kConstOff
 
 struct EldsArgs {
   int n_cols;  // batch * n_edges
@@ -83,12 +79,6 @@ __device__ __forceinline__ const float* chunk_src(const EldsArgs& a, int i) {
   return a.w_out + (size_t)(i - kChunksPerLayer) * kChunkFloats;
 }
 
-// one float per thread of a constant vector, requested like the indices (a load hipcc does not count)
-__device__ __forceinline__ float hld1(const float* p) {
-  float v;
-  asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
 // the counted wait of the prologue: the two indices and the five constants have landed, N younger requests stay in flight
 template <int N>
 __device__ __forceinline__ void wait_prologue(int& s, int& d, float (&c)[5]) {
@@ -99,26 +89,8 @@ template <bool RAW, int NPROJ>
 __global__ __launch_bounds__(kThreads, 2) void elds_kernel(const EldsArgs a) {
   float* const lds = lds_base();
   const float* const cst = lds + kConstOff;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int j = lane & 15;
-  const int q = lane >> 4;
-  int tile = blockIdx.x;
-  if (a.xcd_base > 0) {
-    const int xcd = tile & 7, idx = tile >> 3;
-    tile = xcd * a.xcd_base + (xcd < a.xcd_rem ? xcd : a.xcd_rem) + idx;
-  }
-  const int tile_c0 = tile * kColsPerWG;
-  const int c_raw = tile_c0 + wave * kColsPerWave + j;
-  const bool valid = c_raw < a.n_cols;
-  const int c = valid ? c_raw : a.n_cols - 1;
-  const int b = c / a.n_edges;
-  const int k = c - b * a.n_edges;
-
-  // anti-phase start of the second batch of workgroups (see chain_kernel)
-  if (a.stagger > 0 && (blockIdx.x >> 8) == 1) {
-    for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  }
+  GW_TILE_COORDS(a.n_cols, a.n_edges, a.xcd_base, a.xcd_rem)
+  stagger_start(a.stagger);
 
   // ---- prologue.  Issue order matters for the counted waits (vmcnt retires in order) ----
   int s_idx = hldi(a.src + k);
@@ -135,14 +107,7 @@ __global__ __launch_bounds__(kThreads, 2) void elds_kernel(const EldsArgs a) {
   issue_chunk32k(chunk_src<RAW>(a, 0), lds, lane, wave);
   int ci = 0;  // chunk counter of this tile (wave uniform); chunk i lives in LDS buffer i & 1
   wait_prologue<8>(s_idx, d_idx, cv);  // the 8 DMA pieces stay in flight
-  {
-    float* cw = lds + kConstOff + threadIdx.x;  // visible to the workgroup after the first lds_barrier()
-    cw[kB1] = cv[0];
-    cw[kBMid] = cv[1];
-    cw[kBOut] = cv[2];
-    cw[kGamma] = cv[3];
-    cw[kBeta] = cv[4];
-  }
+  consts_to_lds(lds, 0, cv);
 
   const float* prow[NPROJ];
 #pragma unroll
@@ -155,13 +120,6 @@ __global__ __launch_bounds__(kThreads, 2) void elds_kernel(const EldsArgs a) {
   // ring[s & 1][p][h]: features 32s + 16h + 4q .. +3 of projected operand p = its part of the B operand of produce
   // chunk s.  Slice s is requested when slice s-2 has been consumed (end of chunk s-3) and consumed at the end of chunk s-1.
   f32x4 ring[2][NPROJ][2];
-#define GW_REQUEST_SLICE(slot, slice)                                          \
-  {                                                                            \
-    _Pragma("unroll") for (int p = 0; p < NPROJ; ++p) {                        \
-      ring[slot][p][0] = hld4<128 * (slice)>(prow[p]);                         \
-      ring[slot][p][1] = hld4<128 * (slice) + 64>(prow[p]);                    \
-    }                                                                          \
-  }
   // non-raw form: the layer-1 bias of slice `slice` from LDS (two registers, read one chunk before they are added)
 #define GW_BIAS_SLICE(slice)                                                   \
   if (!RAW) {                                                                  \
@@ -305,103 +263,17 @@ __global__ __launch_bounds__(kThreads, 2) void elds_kernel(const EldsArgs a) {
   wait_regs<0>(rres);
 
   // ---- bias, LayerNorm over the 256 features of each column (eps 1e-5, biased variance), residual ----
-  {
 #pragma unroll
-    for (int t = 0; t < 16; ++t) o[t] += *(const f32x4*)(cst + kBOut + 16 * t + 4 * q);
-    constexpr float inv_n = 1.0f / 256.0f;
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) s += (o[t].x + o[t].y) + (o[t].z + o[t].w);
-    s += __shfl_xor(s, 16);
-    s += __shfl_xor(s, 32);
-    const float mean = s * inv_n;
-    float v = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = o[t][r] - mean;
-        v += d * d;
-      }
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    const float rstd = 1.0f / sqrtf(v * inv_n + 1e-5f);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const f32x4 gm = *(const f32x4*)(cst + kGamma + 16 * t + 4 * q);
-      const f32x4 bt = *(const f32x4*)(cst + kBeta + 16 * t + 4 * q);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[t][r] = (o[t][r] - mean) * rstd * gm[r] + bt[r] + rres[t][r];
-    }
-  }
+  for (int t = 0; t < 16; ++t) o[t] += *(const f32x4*)(cst + kBOut + 16 * t + 4 * q);
+  GW_LAYERNORM256(o, GW_LDS4, cst + kGamma, cst + kBeta, + rres[t][r])
 
-  // ---- stage e' through LDS: [64 columns][260] + 64 global destination ids ----
-  __syncthreads();  // every wave is done reading the weight buffers
-  {
-    float* srow = lds + (wave * kColsPerWave + j) * kStageLd + 4 * q;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) *(f32x4*)(srow + 16 * t) = o[t];
-    if (q == 0) ((int*)(lds + kStageFloats))[wave * kColsPerWave + j] = gd_id;
-  }
-  __syncthreads();
-  const int* gdl = (const int*)(lds + kStageFloats);
-
-  // e_out rows: one 1 KiB coalesced store per row (wave w writes the rows of its own 16 columns)
-  if (a.e_out != nullptr) {
-#pragma unroll 4
-    for (int i = 0; i < kColsPerWave; ++i) {
-      const int col = wave * kColsPerWave + i;
-      if (tile_c0 + col < a.n_cols) {
-        const f32x4 vv = *(const f32x4*)(lds + col * kStageLd + 4 * lane);
-        stg4(a.e_out + (size_t)(tile_c0 + col) * 256 + 4 * lane, vv);
-      }
-    }
-  }
-
-  // segment sum: thread f owns feature f; columns are sorted by global destination id, so equal ids form runs.
-  // Interior runs belong to this tile alone -> plain stores; the first and the last run may continue in the
-  // neighbouring tiles -> atomics (agg is zero-filled by the caller).  See edge_kernel for the ballot walk.
-  {
-    const int f = threadIdx.x;
-    float vv[kColsPerWG];
-#pragma unroll
-    for (int i = 0; i < kColsPerWG; ++i) vv[i] = lds[i * kStageLd + f];
-    const int gdv = gdl[lane];
-    const int gdn = gdl[lane < kColsPerWG - 1 ? lane + 1 : lane];
-    const unsigned long long ends = __ballot(lane == kColsPerWG - 1 || gdn != gdv);  // bit i: a run ends with column i
-    float run = 0.f;
-    bool first = true;
-#pragma unroll
-    for (int i = 0; i < kColsPerWG; ++i) {
-      run += vv[i];
-      if (__builtin_expect((ends >> i) & 1ull, 0)) {
-        const int cur = __builtin_amdgcn_readlane(gdv, i);
-        if (cur >= 0) {
-          float* dstp = a.agg + (size_t)cur * 256 + f;
-          if (first || i == kColsPerWG - 1) {
-            __hip_atomic_fetch_add((GW_AS1 float*)dstp, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          } else {
-            stg1(dstp, run);
-          }
-        }
-        first = false;
-        run = 0.f;
-      }
-    }
-  }
-#undef GW_REQUEST_SLICE
+  // ---- stage e' through LDS, e_out rows, segment sum ----
+  GW_STAGE_ROWS(o, gd_id)
+  if (a.e_out != nullptr) store_e_rows(lds, a.e_out, tile_c0, a.n_cols, wave, lane);
+  GW_SEGMENT_SUM_ATOMICS(a.agg)
 #undef GW_BIAS_SLICE
 #undef GW_CONSUME_SLICE
 #undef GW_PRODUCE_CHUNK
-}
-
-template <typename K>
-int launch(K kernel, const EldsArgs& a, void* stream) {
-  static DeviceOnce once;  // per template instantiation and device
-  if (once.first()) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kEldsLdsBytes);
-  const int grid = (a.n_cols + kColsPerWG - 1) / kColsPerWG;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), kEldsLdsBytes, (hipStream_t)stream, a);
-  return check_launch("elds_kernel launch");
 }
 
 inline bool f32_rows(const gw_operand* op) { return op->layout == GW_LAYOUT_ROWS_F32; }
@@ -478,25 +350,13 @@ int edge_lds_launch(int32_t batch, int32_t n_edges, const int32_t* src, const in
   a.res_ld = e_res->ld;
   a.e_out = e_out;
   a.agg = agg;
-  {
-    static const int skip = GW_TUNE("GW_EDGE_SKIP", 0);
-    static const int dma6 = GW_TUNE("GW_EDGE_DMA6", 0);
-    a.skip = skip == 4 || skip == 5 ? skip : 0;  // (only the chunk macro's switches apply here)
-    a.dma6 = dma6;
-  }
-  {
-    static const int stagger_override = GW_TUNE("GW_STAGGER", -1);
-    const int passes = 2 + n_raw;  // [raw layer-1 pass +] middle layer + output layer
-    a.stagger = stagger_override >= 0 ? stagger_override * passes : 2 * passes + 2;
-    if (tiles <= 256) a.stagger = 0;
-  }
-  {
-    static const int xcd_map = GW_TUNE("GW_XCD_MAP", 1);  // 0: workgroup i takes tile i (A/B measurements)
-    a.xcd_base = (xcd_map != 0 && tiles >= 64) ? tiles / 8 : 0;
-    a.xcd_rem = tiles % 8;
-  }
-  if (n_raw == 1) return n_proj == 1 ? launch(elds_kernel<true, 1>, a, stream) : launch(elds_kernel<true, 2>, a, stream);
-  return launch(elds_kernel<false, 3>, a, stream);
+  fill_tile_schedule(a, tiles, 2 + n_raw);     // [raw layer-1 pass +] middle layer + output layer
+  if (a.skip != 4 && a.skip != 5) a.skip = 0;  // (only the chunk macro's switches apply here)
+  const char* what = "elds_kernel launch";
+  if (n_raw == 1)
+    return n_proj == 1 ? launch_tile_kernel(elds_kernel<true, 1>, a, kEldsLdsBytes, what, stream)
+                       : launch_tile_kernel(elds_kernel<true, 2>, a, kEldsLdsBytes, what, stream);
+  return launch_tile_kernel(elds_kernel<false, 3>, a, kEldsLdsBytes, what, stream);
 }
 
 }  // namespace gw

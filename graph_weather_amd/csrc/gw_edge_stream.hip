@@ -24,10 +24,7 @@ using namespace gw;
 
 namespace {
 
-constexpr int kConstFloats = 5 * 256;                          // b1 | b_mid | b_out | gamma | beta
-constexpr int kConstOff = kStageFloats + kColsPerWG;           // behind the staging area and the 64 destination ids
-constexpr int kStreamLdsBytes = (kConstOff + kConstFloats) * 4;
-static_assert((kConstOff * 4) % 16 == 0, "constants are read as 16-byte vectors");
+constexpr int kStreamLdsBytes = (kConstOff + kConstSetFloats) * 4;  // staging + destination ids + one set of constants
 static_assert(2 * kStreamLdsBytes <= 160 * 1024, "two workgroups per CU must fit the 160 KiB of LDS");
 
 struct StreamArgs {
@@ -66,26 +63,8 @@ template <int NPROJ>
 __global__ __launch_bounds__(kThreads, 2) void estream_kernel(const StreamArgs a) {
   float* const lds = lds_base();
   const float* const cst = lds + kConstOff;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int j = lane & 15;
-  const int q = lane >> 4;
-  int tile = blockIdx.x;
-  if (a.xcd_base > 0) {
-    const int xcd = tile & 7, idx = tile >> 3;
-    tile = xcd * a.xcd_base + (xcd < a.xcd_rem ? xcd : a.xcd_rem) + idx;
-  }
-  const int tile_c0 = tile * kColsPerWG;
-  const int c_raw = tile_c0 + wave * kColsPerWave + j;
-  const bool valid = c_raw < a.n_cols;
-  const int c = valid ? c_raw : a.n_cols - 1;
-  const int b = c / a.n_edges;
-  const int k = c - b * a.n_edges;
-
-  // anti-phase start of the second batch of workgroups (see chain_kernel)
-  if (a.stagger > 0 && (blockIdx.x >> 8) == 1) {
-    for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  }
+  GW_TILE_COORDS(a.n_cols, a.n_edges, a.xcd_base, a.xcd_rem)
+  stagger_start(a.stagger);
 
   // ---- prologue.  Issue order matters for the counted waits (vmcnt retires in order) ----
   int s_idx = hldi(a.src + k);
@@ -93,13 +72,9 @@ __global__ __launch_bounds__(kThreads, 2) void estream_kernel(const StreamArgs a
   issue_chunk32k(chunk_src(a, 0), lds, lane, wave);
   int ci = 0;  // chunk counter of this tile (wave uniform); chunk i lives in LDS buffer i & 1
   {  // constants to LDS while the indices travel (hipcc counts these loads: its wait in front of the LDS writes is a full drain)
-    float* cw = lds + kConstOff;
     const int f = threadIdx.x;
-    cw[f] = ldg1(a.b1 + f);
-    cw[256 + f] = ldg1(a.b_mid + f);
-    cw[512 + f] = ldg1(a.b_out + f);
-    cw[768 + f] = ldg1(a.gamma + f);
-    cw[1024 + f] = ldg1(a.beta + f);
+    const float cv[5] = {ldg1(a.b1 + f), ldg1(a.b_mid + f), ldg1(a.b_out + f), ldg1(a.gamma + f), ldg1(a.beta + f)};
+    consts_to_lds(lds, 0, cv);
   }
   wait_regs<0>(s_idx, d_idx);
 
@@ -114,18 +89,11 @@ __global__ __launch_bounds__(kThreads, 2) void estream_kernel(const StreamArgs a
   // ring[s & 1][p][h]: features 32s + 16h + 4q .. +3 of projected operand p = its part of the B operand of produce
   // chunk s.  Slice s is requested when slice s-2 has been consumed (end of chunk s-3) and consumed at the end of chunk s-1.
   f32x4 ring[2][NPROJ][2];
-#define GW_REQUEST_SLICE(slot, slice)                                          \
-  {                                                                            \
-    _Pragma("unroll") for (int p = 0; p < NPROJ; ++p) {                        \
-      ring[slot][p][0] = hld4<128 * (slice)>(prow[p]);                         \
-      ring[slot][p][1] = hld4<128 * (slice) + 64>(prow[p]);                    \
-    }                                                                          \
-  }
   // the layer-1 bias of slice `slice` from LDS (two registers, read one chunk before they are added)
 #define GW_BIAS_SLICE(slice)                                                   \
   {                                                                            \
-    bb0 = *(const f32x4*)(cst + 32 * (slice) + 4 * q);                         \
-    bb1 = *(const f32x4*)(cst + 32 * (slice) + 16 + 4 * q);                    \
+    bb0 = *(const f32x4*)(cst + kB1 + 32 * (slice) + 4 * q);                   \
+    bb1 = *(const f32x4*)(cst + kB1 + 32 * (slice) + 16 + 4 * q);              \
   }
   // B operand of produce chunk `slice` from ring slot `slot`: the bias is added last, as in edge_kernel
 #define GW_CONSUME_SLICE(slot, slice)                                          \
@@ -152,7 +120,7 @@ __global__ __launch_bounds__(kThreads, 2) void estream_kernel(const StreamArgs a
   wait_regs<2 * NPROJ>(ring[0]);  // chunk 0 and slice 0 have landed; slice 1 stays in flight
   lds_barrier();                  // ... everybody's share of chunk 0 and of the constants
 #pragma unroll
-  for (int t = 0; t < 16; ++t) acc2[t] = *(const f32x4*)(cst + 256 + 16 * t + 4 * q);
+  for (int t = 0; t < 16; ++t) acc2[t] = *(const f32x4*)(cst + kBMid + 16 * t + 4 * q);
   GW_BIAS_SLICE(0)
 #pragma unroll
   for (int b4 = 0; b4 < 4; ++b4) a_cur[b4] = *(const f32x4*)(lds + lane * 4 + b4 * 256);
@@ -206,92 +174,15 @@ __global__ __launch_bounds__(kThreads, 2) void estream_kernel(const StreamArgs a
     }
   }
 
-  // ---- bias, LayerNorm over the 256 features of each column (eps 1e-5, biased variance) ----
-  {
+  // ---- bias, LayerNorm, staging through LDS, segment sum ----
 #pragma unroll
-    for (int t = 0; t < 16; ++t) o[t] += *(const f32x4*)(cst + 512 + 16 * t + 4 * q);
-    constexpr float inv_n = 1.0f / 256.0f;
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) s += (o[t].x + o[t].y) + (o[t].z + o[t].w);
-    s += __shfl_xor(s, 16);
-    s += __shfl_xor(s, 32);
-    const float mean = s * inv_n;
-    float v = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = o[t][r] - mean;
-        v += d * d;
-      }
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    const float rstd = 1.0f / sqrtf(v * inv_n + 1e-5f);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const f32x4 gm = *(const f32x4*)(cst + 768 + 16 * t + 4 * q);
-      const f32x4 bt = *(const f32x4*)(cst + 1024 + 16 * t + 4 * q);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[t][r] = (o[t][r] - mean) * rstd * gm[r] + bt[r];
-    }
-  }
-
-  // ---- stage the rows through LDS: [64 columns][260] + 64 global destination ids ----
-  __syncthreads();  // every wave is done reading the weight buffers
-  {
-    float* srow = lds + (wave * kColsPerWave + j) * kStageLd + 4 * q;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) *(f32x4*)(srow + 16 * t) = o[t];
-    if (q == 0) ((int*)(lds + kStageFloats))[wave * kColsPerWave + j] = gd_id;
-  }
-  __syncthreads();
-  const int* gdl = (const int*)(lds + kStageFloats);
-
-  // segment sum: thread f owns feature f; columns are sorted by global destination id, so equal ids form runs.
-  // Interior runs belong to this tile alone -> plain stores; the first and the last run may continue in the
-  // neighbouring tiles -> atomics (agg is zero-filled by the caller).  See edge_kernel for the ballot walk.
-  {
-    const int f = threadIdx.x;
-    float vv[kColsPerWG];
-#pragma unroll
-    for (int i = 0; i < kColsPerWG; ++i) vv[i] = lds[i * kStageLd + f];
-    const int gdv = gdl[lane];
-    const int gdn = gdl[lane < kColsPerWG - 1 ? lane + 1 : lane];
-    const unsigned long long ends = __ballot(lane == kColsPerWG - 1 || gdn != gdv);  // bit i: a run ends with column i
-    float run = 0.f;
-    bool first = true;
-#pragma unroll
-    for (int i = 0; i < kColsPerWG; ++i) {
-      run += vv[i];
-      if (__builtin_expect((ends >> i) & 1ull, 0)) {
-        const int cur = __builtin_amdgcn_readlane(gdv, i);
-        if (cur >= 0) {
-          float* dstp = a.agg + (size_t)cur * 256 + f;
-          if (first || i == kColsPerWG - 1) {
-            __hip_atomic_fetch_add((GW_AS1 float*)dstp, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          } else {
-            stg1(dstp, run);
-          }
-        }
-        first = false;
-        run = 0.f;
-      }
-    }
-  }
-#undef GW_REQUEST_SLICE
+  for (int t = 0; t < 16; ++t) o[t] += *(const f32x4*)(cst + kBOut + 16 * t + 4 * q);
+  GW_LAYERNORM256(o, GW_LDS4, cst + kGamma, cst + kBeta, )
+  GW_STAGE_ROWS(o, gd_id)
+  GW_SEGMENT_SUM_ATOMICS(a.agg)
 #undef GW_BIAS_SLICE
 #undef GW_CONSUME_SLICE
 #undef GW_PRODUCE_CHUNK
-}
-
-template <typename K>
-int launch(K kernel, const StreamArgs& a, void* stream) {
-  static DeviceOnce once;  // per template instantiation and device
-  if (once.first()) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kStreamLdsBytes);
-  const int grid = (a.n_cols + kColsPerWG - 1) / kColsPerWG;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), kStreamLdsBytes, (hipStream_t)stream, a);
-  return check_launch("estream_kernel launch");
 }
 
 inline bool is_proj_f32(const gw_operand* op) { return op->k > 0 && op->projected && op->layout == GW_LAYOUT_ROWS_F32; }
@@ -344,24 +235,11 @@ int edge_stream_launch(int32_t batch, int32_t n_edges, const int32_t* src, const
   a.gamma = w->ln_gamma;
   a.beta = w->ln_beta;
   a.agg = agg;
-  {
-    static const int skip = GW_TUNE("GW_EDGE_SKIP", 0);
-    static const int dma6 = GW_TUNE("GW_EDGE_DMA6", 0);
-    a.skip = skip == 4 || skip == 5 ? skip : 0;  // (only the chunk macro's switches apply here)
-    a.dma6 = dma6;
-  }
-  {
-    static const int stagger_override = GW_TUNE("GW_STAGGER", -1);
-    const int passes = 2;  // middle layer + output layer
-    a.stagger = stagger_override >= 0 ? stagger_override * passes : 2 * passes + 2;
-    if (tiles <= 256) a.stagger = 0;
-  }
-  {
-    static const int xcd_map = GW_TUNE("GW_XCD_MAP", 1);  // 0: workgroup i takes tile i (A/B measurements)
-    a.xcd_base = (xcd_map != 0 && tiles >= 64) ? tiles / 8 : 0;
-    a.xcd_rem = tiles % 8;
-  }
-  return n_proj == 1 ? launch(estream_kernel<1>, a, stream) : launch(estream_kernel<2>, a, stream);
+  fill_tile_schedule(a, tiles, 2);            // middle layer + output layer
+  if (a.skip != 4 && a.skip != 5) a.skip = 0;  // (only the chunk macro's switches apply here)
+  const char* what = "estream_kernel launch";
+  return n_proj == 1 ? launch_tile_kernel(estream_kernel<1>, a, kStreamLdsBytes, what, stream)
+                     : launch_tile_kernel(estream_kernel<2>, a, kStreamLdsBytes, what, stream);
 }
 
 }  // namespace gw

@@ -28,14 +28,10 @@ using namespace gw;
 namespace {
 
 constexpr int kNodeSteps = 28;                                 // K-steps of the node encoder's first layer (17 .. 112 features)
-constexpr int kConstFloats = 10 * 256;                         // node encoder: b1 | b_mid | b_out | gamma | beta, then the edge MLP's
-constexpr int kConstOff = kStageFloats + kColsPerWG;           // behind the staging area and the 64 destination ids
-constexpr int kEncfLdsBytes = (kConstOff + kConstFloats) * 4;
+constexpr int kNodeSet = 0, kEdgeSet = kConstSetFloats;        // two sets of constants: the node encoder's, then the edge MLP's
+constexpr int kEncfLdsBytes = (kConstOff + 2 * kConstSetFloats) * 4;
 static_assert(kEncfLdsBytes == 77056, "staging (66 560) + destination ids (256) + constants (10 240)");
-static_assert((kConstOff * 4) % 16 == 0, "constants are read as 16-byte vectors");
 static_assert(2 * kEncfLdsBytes <= 160 * 1024, "two workgroups per CU must fit the 160 KiB of LDS");
-constexpr int kB1 = 0, kBMid = 256, kBOut = 512, kGamma = 768, kBeta = 1024;  // float offsets inside one MLP's set
-constexpr int kNodeSet = 0, kEdgeSet = 1280;                                  // float offsets of the two sets behind kConstOff
 
 struct EncfArgs {
   int n_cols;  // batch * n_edges
@@ -83,12 +79,7 @@ __device__ __forceinline__ const float* chunk_src(const EncfArgs& a, int i) {
   return m + (size_t)(i & 7) * kChunkFloats;
 }
 
-// loads hipcc must not count (gw_edge_common.hpp): one float / one 8-byte pair per thread
-__device__ __forceinline__ float hld1(const float* p) {
-  float v;
-  asm volatile("global_load_dword %0, %1, off" : "=v"(v) : "v"(p) : "memory");
-  return v;
-}
+// loads hipcc must not count (gw_edge_common.hpp): one 8-byte pair per thread
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 hld2(const float* p) {
   f32x2 v;
@@ -157,26 +148,8 @@ template <bool RES, int NPROJ>
 __global__ __launch_bounds__(kThreads, 2) void encfused_kernel(const EncfArgs a) {
   float* const lds = lds_base();
   const float* const cst = lds + kConstOff;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int j = lane & 15;
-  const int q = lane >> 4;
-  int tile = blockIdx.x;
-  if (a.xcd_base > 0) {
-    const int xcd = tile & 7, idx = tile >> 3;
-    tile = xcd * a.xcd_base + (xcd < a.xcd_rem ? xcd : a.xcd_rem) + idx;
-  }
-  const int tile_c0 = tile * kColsPerWG;
-  const int c_raw = tile_c0 + wave * kColsPerWave + j;
-  const bool valid = c_raw < a.n_cols;
-  const int c = valid ? c_raw : a.n_cols - 1;
-  const int b = c / a.n_edges;
-  const int k = c - b * a.n_edges;
-
-  // anti-phase start of the second batch of workgroups (see chain_kernel)
-  if (a.stagger > 0 && (blockIdx.x >> 8) == 1) {
-    for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(127);
-  }
+  GW_TILE_COORDS(a.n_cols, a.n_edges, a.xcd_base, a.xcd_rem)
+  stagger_start(a.stagger);
 
   // ---- prologue.  Issue order matters for the counted waits (vmcnt retires in order) ----
   int s_idx = hldi(a.src + k);
@@ -242,11 +215,8 @@ __global__ __launch_bounds__(kThreads, 2) void encfused_kernel(const EncfArgs a)
     }
   }
   wait_const(cv);  // (everything has landed: chunk 0, the constants, the row)
-  {
-    float* cw = lds + kConstOff + threadIdx.x;  // visible to the workgroup after the first lds_barrier()
-#pragma unroll
-    for (int i = 0; i < 10; ++i) cw[256 * i] = cv[i];
-  }
+  consts_to_lds(lds, kNodeSet, cv);
+  consts_to_lds(lds, kEdgeSet, cv + 5);
   lds_barrier();  // everybody's share of chunk 0 and of the constants
 
   f32x4 a_cur[4];  // A fragments of the next K-step to run
@@ -285,45 +255,13 @@ __global__ __launch_bounds__(kThreads, 2) void encfused_kernel(const EncfArgs a)
     for (int t = 0; t < 16; ++t) o[t] = *(const f32x4*)(cst + kNodeSet + kBOut + 16 * t + 4 * q);
 #pragma unroll
     for (int cc = 0; cc < kChunksPerLayer; ++cc) GW_FCHUNK(o, hin, 8 * cc, 8, 8, 4, wait_vm<0>())
-    // LayerNorm over the 256 features of each column (eps 1e-5, biased variance)
-    constexpr float inv_n = 1.0f / 256.0f;
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) s += (o[t].x + o[t].y) + (o[t].z + o[t].w);
-    s += __shfl_xor(s, 16);
-    s += __shfl_xor(s, 32);
-    const float mean = s * inv_n;
-    float v = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = o[t][r] - mean;
-        v += d * d;
-      }
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    const float rstd = 1.0f / sqrtf(v * inv_n + 1e-5f);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const f32x4 gm = *(const f32x4*)(cst + kNodeSet + kGamma + 16 * t + 4 * q);
-      const f32x4 bt = *(const f32x4*)(cst + kNodeSet + kBeta + 16 * t + 4 * q);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) o[t][r] = (o[t][r] - mean) * rstd * gm[r] + bt[r];
-    }
+    GW_LAYERNORM256(o, GW_LDS4, cst + kNodeSet + kGamma, cst + kNodeSet + kBeta, )
   }
 
   // ================= edge update (elds_kernel<true, NPROJ>'s arithmetic); o = the grid row = its raw operand =================
   // ring[s & 1][p][h]: features 32s + 16h + 4q .. +3 of projected operand p = its part of the B operand of produce
   // chunk s.  Slice s is requested when slice s-2 has been consumed (end of chunk s-3) and consumed at the end of chunk s-1.
   f32x4 ring[2][NPROJ][2];
-#define GW_REQUEST_SLICE(slot, slice)                                          \
-  {                                                                            \
-    _Pragma("unroll") for (int p = 0; p < NPROJ; ++p) {                        \
-      ring[slot][p][0] = hld4<128 * (slice)>(prow[p]);                         \
-      ring[slot][p][1] = hld4<128 * (slice) + 64>(prow[p]);                    \
-    }                                                                          \
-  }
   // B operand of produce chunk `slice` from ring slot `slot`: the layer-1 accumulator tiles (they started from b1) plus the
   // gathered rows
 #define GW_CONSUME_SLICE(slot, slice)                                          \
@@ -423,93 +361,19 @@ __global__ __launch_bounds__(kThreads, 2) void encfused_kernel(const EncfArgs a)
   if (RES) wait_regs<0>(rres);
 
   // ---- bias, LayerNorm over the 256 features of each column (eps 1e-5, biased variance), residual ----
-  {
 #pragma unroll
-    for (int t = 0; t < 16; ++t) o[t] += *(const f32x4*)(cst + kEdgeSet + kBOut + 16 * t + 4 * q);
-    constexpr float inv_n = 1.0f / 256.0f;
-    float s = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) s += (o[t].x + o[t].y) + (o[t].z + o[t].w);
-    s += __shfl_xor(s, 16);
-    s += __shfl_xor(s, 32);
-    const float mean = s * inv_n;
-    float v = 0.f;
-#pragma unroll
-    for (int t = 0; t < 16; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = o[t][r] - mean;
-        v += d * d;
-      }
-    v += __shfl_xor(v, 16);
-    v += __shfl_xor(v, 32);
-    const float rstd = 1.0f / sqrtf(v * inv_n + 1e-5f);
-#pragma unroll
-    for (int t = 0; t < 16; ++t) {
-      const f32x4 gm = *(const f32x4*)(cst + kEdgeSet + kGamma + 16 * t + 4 * q);
-      const f32x4 bt = *(const f32x4*)(cst + kEdgeSet + kBeta + 16 * t + 4 * q);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (RES) o[t][r] = (o[t][r] - mean) * rstd * gm[r] + bt[r] + rres[t][r];
-        else o[t][r] = (o[t][r] - mean) * rstd * gm[r] + bt[r];
-      }
-    }
+  for (int t = 0; t < 16; ++t) o[t] += *(const f32x4*)(cst + kEdgeSet + kBOut + 16 * t + 4 * q);
+  if (RES) {
+    GW_LAYERNORM256(o, GW_LDS4, cst + kEdgeSet + kGamma, cst + kEdgeSet + kBeta, + rres[t][r])
+  } else {
+    GW_LAYERNORM256(o, GW_LDS4, cst + kEdgeSet + kGamma, cst + kEdgeSet + kBeta, )
   }
 
-  // ---- stage e' through LDS: [64 columns][260] + 64 global destination ids ----
-  __syncthreads();  // every wave is done reading the weight buffers
-  {
-    float* srow = lds + (wave * kColsPerWave + j) * kStageLd + 4 * q;
-#pragma unroll
-    for (int t = 0; t < 16; ++t) *(f32x4*)(srow + 16 * t) = o[t];
-    if (q == 0) ((int*)(lds + kStageFloats))[wave * kColsPerWave + j] = gd_id;
-  }
-  __syncthreads();
-  const int* gdl = (const int*)(lds + kStageFloats);
-
-  // segment sum: thread f owns feature f; columns are sorted by global destination id, so equal ids form runs.
-  // Interior runs belong to this tile alone -> plain stores; the first and the last run may continue in the
-  // neighbouring tiles -> atomics (agg is zero-filled by the caller).  See edge_kernel for the ballot walk.
-  {
-    const int f = threadIdx.x;
-    float vv[kColsPerWG];
-#pragma unroll
-    for (int i = 0; i < kColsPerWG; ++i) vv[i] = lds[i * kStageLd + f];
-    const int gdv = gdl[lane];
-    const int gdn = gdl[lane < kColsPerWG - 1 ? lane + 1 : lane];
-    const unsigned long long ends = __ballot(lane == kColsPerWG - 1 || gdn != gdv);  // bit i: a run ends with column i
-    float run = 0.f;
-    bool first = true;
-#pragma unroll
-    for (int i = 0; i < kColsPerWG; ++i) {
-      run += vv[i];
-      if (__builtin_expect((ends >> i) & 1ull, 0)) {
-        const int cur = __builtin_amdgcn_readlane(gdv, i);
-        if (cur >= 0) {
-          float* dstp = a.agg + (size_t)cur * 256 + f;
-          if (first || i == kColsPerWG - 1) {
-            __hip_atomic_fetch_add((GW_AS1 float*)dstp, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          } else {
-            stg1(dstp, run);
-          }
-        }
-        first = false;
-        run = 0.f;
-      }
-    }
-  }
-#undef GW_REQUEST_SLICE
+  // ---- stage e' through LDS, segment sum ----
+  GW_STAGE_ROWS(o, gd_id)
+  GW_SEGMENT_SUM_ATOMICS(a.agg)
 #undef GW_CONSUME_SLICE
 #undef GW_PRODUCE_CHUNK
-}
-
-template <typename K>
-int launch(K kernel, const EncfArgs& a, void* stream) {
-  static DeviceOnce once;  // per template instantiation and device
-  if (once.first()) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kEncfLdsBytes);
-  const int grid = (a.n_cols + kColsPerWG - 1) / kColsPerWG;
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), kEncfLdsBytes, (hipStream_t)stream, a);
-  return check_launch("encfused_kernel launch");
 }
 
 inline bool node_encoder_ok(const gw_mlp_weights* w) {
@@ -598,18 +462,11 @@ int gw_encoder_fused_forward(int32_t batch, int32_t n_edges, const int32_t* src,
     a.res_ld = e_res->ld;
   }
   a.agg = agg;
-  const int tiles = (a.n_cols + kColsPerWG - 1) / kColsPerWG;
-  {
-    static const int stagger_override = GW_TUNE("GW_STAGGER", -1);
-    const int passes = 6;  // 28 of 64 K-steps + five full passes
-    a.stagger = stagger_override >= 0 ? stagger_override * passes : 2 * passes + 2;
-    if (tiles <= 256) a.stagger = 0;
-  }
-  {
-    static const int xcd_map = GW_TUNE("GW_XCD_MAP", 1);  // 0: workgroup i takes tile i (A/B measurements)
-    a.xcd_base = (xcd_map != 0 && tiles >= 64) ? tiles / 8 : 0;
-    a.xcd_rem = tiles % 8;
-  }
-  if (res) return n_proj == 1 ? launch(encfused_kernel<true, 1>, a, stream) : launch(encfused_kernel<true, 2>, a, stream);
-  return n_proj == 1 ? launch(encfused_kernel<false, 1>, a, stream) : launch(encfused_kernel<false, 2>, a, stream);
+  fill_tile_schedule(a, (a.n_cols + kColsPerWG - 1) / kColsPerWG, 6);  // 28 of 64 K-steps + five full passes
+  const char* what = "encfused_kernel launch";
+  if (res)
+    return n_proj == 1 ? launch_tile_kernel(encfused_kernel<true, 1>, a, kEncfLdsBytes, what, stream)
+                       : launch_tile_kernel(encfused_kernel<true, 2>, a, kEncfLdsBytes, what, stream);
+  return n_proj == 1 ? launch_tile_kernel(encfused_kernel<false, 1>, a, kEncfLdsBytes, what, stream)
+                     : launch_tile_kernel(encfused_kernel<false, 2>, a, kEncfLdsBytes, what, stream);
 }
