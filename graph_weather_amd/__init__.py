@@ -54,6 +54,7 @@ from .aurora import (  # noqa: F401  (csrc/gw_aurora.hip, csrc/gw_conv3d.hip, ma
     Swin3DEncoder,
 )
 from . import gencast  # noqa: F401  (csrc/gw_gencast.hip; its Encoder / Processor / Decoder / MLP stay in the module: the names above are the forecaster's)
+from . import gencast_graphs, gencast_model  # noqa: F401  (GenCast's GraphBuilder and Denoiser: batch-shared route of csrc/gw_gencast.hip)
 from .graphed import ForwardGraph  # noqa: F401  (the inference forward as one HIP graph)
 from .rollout import rollout  # noqa: F401
 from .optim import AdamW  # noqa: F401

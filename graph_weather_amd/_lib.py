@@ -51,6 +51,9 @@ EXPORTS = [
     "gw_graph_attention_forward", "gw_graph_attention_backward", "gw_cond_layernorm_forward", "gw_cond_layernorm_backward",
     "gw_beta_gate_forward", "gw_beta_gate_workspace_bytes", "gw_beta_gate_backward", "gw_silu_forward", "gw_silu_backward",
     "gw_fourier_forward", "gw_fourier_backward",
+    "gw_graph_attention_batched_forward", "gw_graph_attention_batched_backward", "gw_cond_layernorm_grouped_forward",
+    "gw_cond_layernorm_grouped_workspace_bytes", "gw_cond_layernorm_grouped_backward", "gw_gencast_precond_input_forward",
+    "gw_gencast_precond_input_backward", "gw_gencast_precond_output_forward", "gw_gencast_precond_output_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -415,6 +418,27 @@ def lib():
     L.gw_graph_attention_backward.restype = c_int
     L.gw_graph_attention_backward.argtypes = [c_int32] * 5 + [c_void_p] * 6 + [c_void_p, c_int32] * 4 + [
         c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p] + [c_void_p, c_int32] * 4 + [c_void_p]
+    L.gw_graph_attention_batched_forward.restype = c_int
+    L.gw_graph_attention_batched_forward.argtypes = [c_int32, c_int64] + L.gw_graph_attention_forward.argtypes
+    L.gw_graph_attention_batched_backward.restype = c_int
+    L.gw_graph_attention_batched_backward.argtypes = [c_int32, c_int64] + L.gw_graph_attention_backward.argtypes
+    L.gw_cond_layernorm_grouped_forward.restype = c_int
+    L.gw_cond_layernorm_grouped_forward.argtypes = [c_int64, c_int32, c_int32, c_int64] + [c_void_p, c_int32] * 4 + [c_void_p]
+    L.gw_cond_layernorm_grouped_workspace_bytes.restype = c_size_t
+    L.gw_cond_layernorm_grouped_workspace_bytes.argtypes = [c_int64, c_int32, c_int64]
+    L.gw_cond_layernorm_grouped_backward.restype = c_int
+    L.gw_cond_layernorm_grouped_backward.argtypes = [c_int64, c_int32, c_int32, c_int64] + [c_void_p, c_int32] * 4 + [
+        c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]
+    L.gw_gencast_precond_input_forward.restype = c_int
+    L.gw_gencast_precond_input_forward.argtypes = [c_int32, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p] + [
+        c_void_p, c_int32] * 4 + [c_void_p, c_void_p]
+    L.gw_gencast_precond_input_backward.restype = c_int
+    L.gw_gencast_precond_input_backward.argtypes = [c_int32, c_int64, c_int32, c_int32, c_float, c_void_p] + [c_void_p, c_int32] * 3 + [
+        c_void_p]
+    L.gw_gencast_precond_output_forward.restype = c_int
+    L.gw_gencast_precond_output_forward.argtypes = [c_int32, c_int64, c_int32, c_float, c_void_p] + [c_void_p, c_int32] * 3 + [c_void_p]
+    L.gw_gencast_precond_output_backward.restype = c_int
+    L.gw_gencast_precond_output_backward.argtypes = [c_int32, c_int64, c_int32, c_float, c_void_p] + [c_void_p, c_int32] * 3 + [c_void_p]
     L.gw_cond_layernorm_forward.restype = c_int
     L.gw_cond_layernorm_forward.argtypes = [c_int64, c_int32, c_int32] + [c_void_p, c_int32] * 4 + [c_void_p]
     L.gw_cond_layernorm_backward.restype = c_int

@@ -14,8 +14,16 @@
 //   attn_*_long_kernel   rows too long for register fragments (a scalar dim_head above 512, any above 2048): one wave per workgroup,
 //                        running rows in LDS, everything else streamed - coverage up to heads * dim_head = 4096.
 //   A destination with many edges is one wave's serial walk: correct at any degree, fast only for near-uniform degrees.
+//   Batch-shared form (gw_graph_attention_batched_*): `batch` disconnected copies of one graph share the plan; copy b's node rows
+//   start at b n, the work item is (copy, destination, head) with the walk above, and the edge table moves by e_bstride rows per
+//   copy (0: one table for all).  The gradient of a shared table is summed over the copies in copy order by the wave that owns
+//   the destination (it owns the same edges in every copy): plain read-modify-write, no atomics.
 //
-//   cln_*_kernel         ConditionalLayerNorm: act(scale[r] o LN(x[r]) + bias[r]) (LN without affine, eps 1e-5), one wave per row
+//   cln_*_kernel         ConditionalLayerNorm: act(scale[g] o LN(x[r]) + bias[g]) (LN without affine, eps 1e-5), one wave per row;
+//                        g = r / rows_per_group (1: a scale and bias row per row).  Grouped gradient of scale and bias: per-slab
+//                        partials (256 rows of one group, one thread per column, rows in order) added in slab order
+//   precond_*_kernel     the Denoiser's preconditioning (Karras et al. 2022) as row kernels: the encoder's grid input rows
+//                        (c_in(sigma_b) Z | X | static grid features) with c_noise, and c_skip(sigma_b) Z + c_out(sigma_b) preds
 //   gate_*_kernel        TransformerConv's beta gate: g = sigmoid(w_a.out + w_b.x_r + w_c.(out - x_r)), y = g x_r + (1 - g) out; the
 //                        weight gradient is per-slab partials (256 rows, one thread per column, rows in order) added in slab order
 //   silu_*, fourier_*    SiLU; cos / sin features of the noise level (accurate cosf / sinf) and their gradient
@@ -134,21 +142,51 @@ struct AttnArgs {
   float *dq, *dk, *dv, *de;
   long long ld_dq, ld_dk, ld_dv, ld_de;
   float sqrt_c;
+  int batch;                 // copies of the graph that share the plan
+  int de_loop;               // destination pass: one wave walks its (destination, head) in every copy and sums de in copy order
+  long long e_bstride;       // rows between the edge tables (e, de) of two copies; 0: one table
+  long long planes;          // batch * n_dst * heads: the distance between the two planes of lse
 };
 
-// grid ceil(items / 4), block 256: wave = one (destination, head), or one destination with its heads in order (head-mean)
+// the arguments of copy b: node tables, planes and scratch move by whole copies, the edge tables by e_bstride rows
+__device__ __forceinline__ AttnArgs attn_copy(AttnArgs a, long long b) {
+  const long long rd = b * a.n_dst, rs = b * a.n_src, eb = b * a.e_bstride;
+  a.q += rd * a.ld_q, a.k += rs * a.ld_k, a.v += rs * a.ld_v;
+  if (a.e != nullptr) a.e += eb * a.ld_e;
+  if (a.out != nullptr) a.out += rd * a.ld_out;
+  if (a.out_heads != nullptr) a.out_heads += rd * a.ld_oh;
+  a.lse += rd * a.heads;
+  if (a.dout != nullptr) a.dout += rd * a.ld_dout;
+  if (a.delta != nullptr) a.delta += rd * a.heads;
+  if (a.dq != nullptr) a.dq += rd * a.ld_dq;
+  if (a.dk != nullptr) a.dk += rs * a.ld_dk;
+  if (a.dv != nullptr) a.dv += rs * a.ld_dv;
+  if (a.de != nullptr) a.de += eb * a.ld_de;
+  return a;
+}
+
+// the copy of a wave's item.  Every lane of a wave holds the same item, but it comes from threadIdx, so the compiler takes it for
+// a per-lane value; read through the first lane the copy is a scalar and the table pointers attn_copy moves stay in SGPRs
+__device__ __forceinline__ long long wave_uniform_copy(long long gitem, long long n_items) {
+  return (long long)__builtin_amdgcn_readfirstlane((int)(gitem / n_items));
+}
+
+// grid ceil(batch items / 4), block 256: wave = one (copy, destination, head), or one (copy, destination) with its heads in order
+// (head-mean)
 template <int NE, bool VEC, int U>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a0) {
   typedef Frag<NE, VEC> F;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long item = (long long)blockIdx.x * 4 + wave;
-  const long long n_items = a.mean ? (long long)a.n_dst : (long long)a.n_dst * a.heads;
-  if (item >= n_items) return;
+  const long long gitem = (long long)blockIdx.x * 4 + wave;
+  const long long n_items = a0.mean ? (long long)a0.n_dst : (long long)a0.n_dst * a0.heads;
+  if (gitem >= n_items * a0.batch) return;
+  const long long copy = wave_uniform_copy(gitem, n_items), item = gitem - copy * n_items;
+  const AttnArgs a = attn_copy(a0, copy);
   const int i = a.mean ? (int)item : (int)(item / a.heads);
   const int h0 = a.mean ? 0 : (int)(item % a.heads), hn = a.mean ? a.heads : 1;
   const int C = a.C;
   const int e0 = ldgi(a.dst_ptr + i), e1 = ldgi(a.dst_ptr + i + 1);
-  const long long planes = (long long)a.n_dst * a.heads;
+  const long long planes = a.planes;
   F macc;
   macc.zero();
   for (int hh = 0; hh < hn; ++hh) {
@@ -211,13 +249,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
   }
 }
 
-// grid ceil(n_dst * heads / 4), block 256
+// one (destination, head) of one copy; de_add: de already holds the sum over the earlier copies
 template <int NE, bool VEC>
-__global__ __launch_bounds__(256) void attn_bwd_dst_kernel(AttnArgs a) {
+__device__ __forceinline__ void attn_bwd_dst_item(const AttnArgs& a, long long item, int lane, bool de_add) {
   typedef Frag<NE, VEC> F;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long item = (long long)blockIdx.x * 4 + wave;
-  if (item >= (long long)a.n_dst * a.heads) return;
   const int i = (int)(item / a.heads), h = (int)(item % a.heads), C = a.C;
   const long long hc = (long long)h * C;
   const int e0 = ldgi(a.dst_ptr + i), e1 = ldgi(a.dst_ptr + i + 1);
@@ -232,7 +267,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dst_kernel(AttnArgs a) {
     delta = wave_sum(dof.dot(of));
   }
   if (lane == 0) a.delta[item] = delta;
-  const float m = a.lse[item], ll = a.lse[(long long)a.n_dst * a.heads + item];
+  const float m = a.lse[item], ll = a.lse[a.planes + item];
   dqf.zero();
   for (int t = e0; t < e1; ++t) {
     const int j = ldgi(a.src + t);
@@ -265,21 +300,50 @@ __global__ __launch_bounds__(256) void attn_bwd_dst_kernel(AttnArgs a) {
       def.zero();
       def.axpy(g, qf);
       def.axpy(p, dof);
+      if (de_add) {
+        F old;
+        old.load(a.de + eid * a.ld_de + hc, C, lane);
+        def.add(old);
+      }
       def.store(a.de + eid * a.ld_de + hc, C, lane);
     }
   }
   dqf.store(a.dq + (long long)i * a.ld_dq + hc, C, lane);
 }
 
-// grid ceil(n_src * heads / 4), block 256; reads delta of attn_bwd_dst_kernel
+// grid ceil(batch n_dst heads / 4), block 256: wave = one (copy, destination, head).  LOOP (a de table shared by the copies): grid
+// ceil(n_dst heads / 4), the wave takes its (destination, head) through the copies in order and sums de by read-modify-write
+template <int NE, bool VEC, bool LOOP>
+__global__ __launch_bounds__(256) void attn_bwd_dst_kernel(AttnArgs a0) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long gitem = (long long)blockIdx.x * 4 + wave;
+  const long long n_items = (long long)a0.n_dst * a0.heads;
+  if constexpr (LOOP) {
+    if (gitem >= n_items) return;
+    for (int b = 0; b < a0.batch; ++b) {
+      const AttnArgs a = attn_copy(a0, b);
+      attn_bwd_dst_item<NE, VEC>(a, gitem, lane, b > 0);
+    }
+  } else {
+    if (gitem >= n_items * a0.batch) return;
+    const long long copy = wave_uniform_copy(gitem, n_items);
+    const AttnArgs a = attn_copy(a0, copy);
+    attn_bwd_dst_item<NE, VEC>(a, gitem - copy * n_items, lane, false);
+  }
+}
+
+// grid ceil(batch n_src heads / 4), block 256; reads delta of attn_bwd_dst_kernel
 template <int NE, bool VEC>
-__global__ __launch_bounds__(256) void attn_bwd_src_kernel(AttnArgs a) {
+__global__ __launch_bounds__(256) void attn_bwd_src_kernel(AttnArgs a0) {
   typedef Frag<NE, VEC> F;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long long item = (long long)blockIdx.x * 4 + wave;
-  if (item >= (long long)a.n_src * a.heads) return;
+  const long long gitem = (long long)blockIdx.x * 4 + wave;
+  const long long n_items = (long long)a0.n_src * a0.heads;
+  if (gitem >= n_items * a0.batch) return;
+  const long long copy = wave_uniform_copy(gitem, n_items), item = gitem - copy * n_items;
+  const AttnArgs a = attn_copy(a0, copy);
   const int j = (int)(item / a.heads), h = (int)(item % a.heads), C = a.C;
-  const long long hc = (long long)h * C, planes = (long long)a.n_dst * a.heads;
+  const long long hc = (long long)h * C, planes = a.planes;
   const int s0 = ldgi(a.src_ptr + j), s1 = ldgi(a.src_ptr + j + 1);
   F kf, vf, dkf, dvf;
   kf.load(a.k + (long long)j * a.ld_k + hc, C, lane);
@@ -322,13 +386,16 @@ __device__ __forceinline__ float row_dot(const float* __restrict__ x, const floa
   return d;
 }
 
-__global__ __launch_bounds__(64) void attn_fwd_long_kernel(AttnArgs a) {
+__global__ __launch_bounds__(64) void attn_fwd_long_kernel(AttnArgs a0) {
   __shared__ float acc[kMaxRow], macc[kMaxRow];
-  const int lane = threadIdx.x, C = a.C;
-  const int i = a.mean ? (int)blockIdx.x : (int)(blockIdx.x / a.heads);
-  const int h0 = a.mean ? 0 : (int)(blockIdx.x % a.heads), hn = a.mean ? a.heads : 1;
+  const int lane = threadIdx.x, C = a0.C;
+  const long long n_items = a0.mean ? (long long)a0.n_dst : (long long)a0.n_dst * a0.heads;
+  const long long copy = blockIdx.x / n_items, item = blockIdx.x - copy * n_items;
+  const AttnArgs a = attn_copy(a0, copy);
+  const int i = a.mean ? (int)item : (int)(item / a.heads);
+  const int h0 = a.mean ? 0 : (int)(item % a.heads), hn = a.mean ? a.heads : 1;
   const int e0 = ldgi(a.dst_ptr + i), e1 = ldgi(a.dst_ptr + i + 1);
-  const long long planes = (long long)a.n_dst * a.heads;
+  const long long planes = a.planes;
   for (int c = lane; c < C; c += 64) macc[c] = 0.f;
   for (int hh = 0; hh < hn; ++hh) {
     const int h = h0 + hh;
@@ -365,10 +432,8 @@ __global__ __launch_bounds__(64) void attn_fwd_long_kernel(AttnArgs a) {
     for (int c = lane; c < C; c += 64) stg1(a.out + (long long)i * a.ld_out + c, macc[c] / (float)a.heads);
 }
 
-__global__ __launch_bounds__(64) void attn_bwd_dst_long_kernel(AttnArgs a) {
-  __shared__ float acc[kMaxRow];
-  const int lane = threadIdx.x, C = a.C;
-  const long long item = blockIdx.x;
+__device__ __forceinline__ void attn_bwd_dst_long_item(const AttnArgs& a, long long item, int lane, bool de_add, float* acc) {
+  const int C = a.C;
   const int i = (int)(item / a.heads), h = (int)(item % a.heads);
   const long long hc = (long long)h * C;
   const int e0 = ldgi(a.dst_ptr + i), e1 = ldgi(a.dst_ptr + i + 1);
@@ -379,7 +444,7 @@ __global__ __launch_bounds__(64) void attn_bwd_dst_long_kernel(AttnArgs a) {
   for (int c = lane; c < C; c += 64) d = fmaf(ldg1(gr + c) / hdiv, ldg1(a.out_heads + (long long)i * a.ld_oh + hc + c), d);
   const float delta = wave_sum(d);
   if (lane == 0) a.delta[item] = delta;
-  const float m = a.lse[item], ll = a.lse[(long long)a.n_dst * a.heads + item];
+  const float m = a.lse[item], ll = a.lse[a.planes + item];
   for (int c = lane; c < C; c += 64) acc[c] = 0.f;
   for (int t = e0; t < e1; ++t) {
     const int j = ldgi(a.src + t);
@@ -392,18 +457,41 @@ __global__ __launch_bounds__(64) void attn_bwd_dst_long_kernel(AttnArgs a) {
     const float g = p * (dp - delta) / a.sqrt_c;
     for (int c = lane; c < C; c += 64) {
       acc[c] = fmaf(g, ldg1(kr + c) + (er != nullptr ? ldg1(er + c) : 0.f), acc[c]);
-      if (a.de != nullptr) stg1(a.de + eid * a.ld_de + hc + c, fmaf(p, ldg1(gr + c) / hdiv, g * ldg1(qr + c)));
+      if (a.de != nullptr) {
+        float* dp_ = a.de + eid * a.ld_de + hc + c;
+        const float dv_ = fmaf(p, ldg1(gr + c) / hdiv, g * ldg1(qr + c));
+        stg1(dp_, de_add ? dv_ + ldg1(dp_) : dv_);
+      }
     }
   }
   for (int c = lane; c < C; c += 64) stg1(a.dq + (long long)i * a.ld_dq + hc + c, acc[c]);
 }
 
-__global__ __launch_bounds__(64) void attn_bwd_src_long_kernel(AttnArgs a) {
+template <bool LOOP>
+__global__ __launch_bounds__(64) void attn_bwd_dst_long_kernel(AttnArgs a0) {
+  __shared__ float acc[kMaxRow];
+  const int lane = threadIdx.x;
+  const long long n_items = (long long)a0.n_dst * a0.heads;
+  if constexpr (LOOP) {
+    for (int b = 0; b < a0.batch; ++b) {
+      const AttnArgs a = attn_copy(a0, b);
+      attn_bwd_dst_long_item(a, blockIdx.x, lane, b > 0, acc);
+    }
+  } else {
+    const long long copy = blockIdx.x / n_items;
+    const AttnArgs a = attn_copy(a0, copy);
+    attn_bwd_dst_long_item(a, blockIdx.x - copy * n_items, lane, false, acc);
+  }
+}
+
+__global__ __launch_bounds__(64) void attn_bwd_src_long_kernel(AttnArgs a0) {
   __shared__ float acck[kMaxRow], accv[kMaxRow];
-  const int lane = threadIdx.x, C = a.C;
-  const long long item = blockIdx.x;
+  const int lane = threadIdx.x, C = a0.C;
+  const long long n_items = (long long)a0.n_src * a0.heads;
+  const long long copy = blockIdx.x / n_items, item = blockIdx.x - copy * n_items;
+  const AttnArgs a = attn_copy(a0, copy);
   const int j = (int)(item / a.heads), h = (int)(item % a.heads);
-  const long long hc = (long long)h * C, planes = (long long)a.n_dst * a.heads;
+  const long long hc = (long long)h * C, planes = a.planes;
   const int s0 = ldgi(a.src_ptr + j), s1 = ldgi(a.src_ptr + j + 1);
   const float* kr = a.k + (long long)j * a.ld_k + hc;
   const float* vr = a.v + (long long)j * a.ld_v + hc;
@@ -482,16 +570,17 @@ __device__ __forceinline__ void row_stats(const float* __restrict__ xr, int widt
 
 __global__ __launch_bounds__(256) void cln_fwd_kernel(long long rows, int width, int act, const float* __restrict__ x, long long ld_x,
                                                       const float* __restrict__ scale, long long ld_s, const float* __restrict__ bias,
-                                                      long long ld_b, float* __restrict__ out, long long ld_o) {
+                                                      long long ld_b, float* __restrict__ out, long long ld_o, long long rpg) {
   const int lane = threadIdx.x & 63;
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
+  const long long g = rpg == 1 ? r : r / rpg;  // the row of scale and bias
   const float* xr = x + r * ld_x;
   float mean, rstd;
   row_stats(xr, width, lane, mean, rstd);
   for (int c = lane; c < width; c += 64) {
     const float xh = (ldg1(xr + c) - mean) * rstd;
-    stg1(out + r * ld_o + c, act_f(ldg1(scale + r * ld_s + c) * xh + ldg1(bias + r * ld_b + c), act));
+    stg1(out + r * ld_o + c, act_f(ldg1(scale + g * ld_s + c) * xh + ldg1(bias + g * ld_b + c), act));
   }
 }
 
@@ -499,17 +588,21 @@ __global__ __launch_bounds__(256) void cln_bwd_kernel(long long rows, int width,
                                                       const float* __restrict__ scale, long long ld_s, const float* __restrict__ bias,
                                                       long long ld_b, const float* __restrict__ dout, long long ld_do,
                                                       float* __restrict__ dx, long long ld_dx, float* __restrict__ dscale,
-                                                      float* __restrict__ dbias, long long ld_dsb) {
+                                                      float* __restrict__ dbias, long long ld_dsb, long long rpg,
+                                                      float* __restrict__ stats) {
+  // rpg > 1 (grouped): dscale and dbias are NULL here - cln_cols_kernel forms them from stats [rows][2] = (mean, rstd)
   const int lane = threadIdx.x & 63;
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
+  const long long gr = rpg == 1 ? r : r / rpg;
   const float* xr = x + r * ld_x;
   float mean, rstd;
   row_stats(xr, width, lane, mean, rstd);
+  if (stats != nullptr && lane == 0) stats[2 * r] = mean, stats[2 * r + 1] = rstd;
   float sa = 0.f, sb = 0.f;
   for (int c = lane; c < width; c += 64) {
-    const float xh = (ldg1(xr + c) - mean) * rstd, sc = ldg1(scale + r * ld_s + c);
-    const float dz = ldg1(dout + r * ld_do + c) * act_d(sc * xh + ldg1(bias + r * ld_b + c), act);
+    const float xh = (ldg1(xr + c) - mean) * rstd, sc = ldg1(scale + gr * ld_s + c);
+    const float dz = ldg1(dout + r * ld_do + c) * act_d(sc * xh + ldg1(bias + gr * ld_b + c), act);
     if (dscale != nullptr) stg1(dscale + r * ld_dsb + c, dz * xh);
     if (dbias != nullptr) stg1(dbias + r * ld_dsb + c, dz);
     const float g = dz * sc;
@@ -520,10 +613,135 @@ __global__ __launch_bounds__(256) void cln_bwd_kernel(long long rows, int width,
   sa = wave_sum(sa) / (float)width;
   sb = wave_sum(sb) / (float)width;
   for (int c = lane; c < width; c += 64) {
-    const float xh = (ldg1(xr + c) - mean) * rstd, sc = ldg1(scale + r * ld_s + c);
-    const float g = ldg1(dout + r * ld_do + c) * act_d(sc * xh + ldg1(bias + r * ld_b + c), act) * sc;
+    const float xh = (ldg1(xr + c) - mean) * rstd, sc = ldg1(scale + gr * ld_s + c);
+    const float g = ldg1(dout + r * ld_do + c) * act_d(sc * xh + ldg1(bias + gr * ld_b + c), act) * sc;
     stg1(dx + r * ld_dx + c, rstd * (g - sa - xh * sb));
   }
+}
+
+// part[group][slab][2][width]: one thread per column walks the rows of one slab of one group in order
+__global__ __launch_bounds__(256) void cln_cols_kernel(long long rows, int width, int act, long long rpg, const float* __restrict__ x,
+                                                       long long ld_x, const float* __restrict__ scale, long long ld_s,
+                                                       const float* __restrict__ bias, long long ld_b, const float* __restrict__ dout,
+                                                       long long ld_do, const float* __restrict__ stats, float* __restrict__ part) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= width) return;
+  const long long g = blockIdx.z, g0 = g * rpg, g1 = g0 + rpg < rows ? g0 + rpg : rows;
+  const long long r0 = g0 + (long long)blockIdx.y * kGateSlab, r1 = r0 + kGateSlab < g1 ? r0 + kGateSlab : g1;
+  const float sc = ldg1(scale + g * ld_s + c), bi = ldg1(bias + g * ld_b + c);
+  double a = 0.0, b = 0.0;  // (fp64 for the reason given at gate_cols_kernel)
+  for (long long r = r0; r < r1; ++r) {
+    const float xh = (ldg1(x + r * ld_x + c) - stats[2 * r]) * stats[2 * r + 1];
+    const float dz = ldg1(dout + r * ld_do + c) * act_d(sc * xh + bi, act);
+    a += (double)(dz * xh);
+    b += (double)dz;
+  }
+  float* p = part + (g * gridDim.y + blockIdx.y) * 2 * width;
+  p[c] = (float)a;
+  p[width + c] = (float)b;
+}
+
+// dscale[g], dbias[g] = the group's slab partials added in slab order
+__global__ __launch_bounds__(256) void cln_sum_kernel(int slabs, int width, const float* __restrict__ part, float* __restrict__ dscale,
+                                                      float* __restrict__ dbias, long long ld_dsb) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= width) return;
+  const long long g = blockIdx.y;
+  double a = 0.0, b = 0.0;
+  for (int sl = 0; sl < slabs; ++sl) {
+    const float* p = part + (g * slabs + sl) * 2 * width;
+    a += (double)ldg1(p + c);
+    b += (double)ldg1(p + width + c);
+  }
+  if (dscale != nullptr) dscale[g * ld_dsb + c] = (float)a;
+  if (dbias != nullptr) dbias[g * ld_dsb + c] = (float)b;
+}
+
+bool cln_grouped_ok(int64_t rows, int32_t width, int64_t rpg) {
+  if (rows < 0 || rows >= ((int64_t)1 << 33) || width < 1 || rpg < 1) return false;
+  const int64_t groups = (rows + rpg - 1) / rpg, slabs = (rpg + kGateSlab - 1) / kGateSlab;
+  return groups <= 65535 && slabs <= 65535;
+}
+size_t cln_grouped_bytes(int64_t rows, int32_t width, int64_t rpg) {
+  const int64_t groups = (rows + rpg - 1) / rpg, slabs = (rpg + kGateSlab - 1) / kGateSlab;
+  return ((size_t)rows * 2 + (size_t)groups * (size_t)slabs * 2 * (size_t)width) * sizeof(float);
+}
+
+// ---- the Denoiser's preconditioning (utils/noise.py, denoiser.py): one wave per grid row, sample b = row / grid_rows --------------
+// The coefficients in float32 in the reference's order of operations (the intrinsics keep the compiler from fusing a * b + c):
+//   c_in = 1 / sqrt(s^2 + d^2), c_skip = d^2 / (s^2 + d^2), c_out = s d / sqrt(s^2 + d^2), c_noise = 1/4 log(s); d = sigma_data
+__device__ __forceinline__ float precond_var(float s, float d2) { return __fadd_rn(__fmul_rn(s, s), d2); }
+__device__ __forceinline__ float precond_c_in(float s, float d2) { return __fdiv_rn(1.0f, __fsqrt_rn(precond_var(s, d2))); }
+__device__ __forceinline__ float precond_c_skip(float s, float d2) { return __fdiv_rn(d2, precond_var(s, d2)); }
+__device__ __forceinline__ float precond_c_out(float s, float d, float d2) {
+  return __fdiv_rn(__fmul_rn(s, d), __fsqrt_rn(precond_var(s, d2)));
+}
+
+// out[r] = (c_in(sigma_b) z[r] | x[r] | stat[r mod grid_rows]); c_noise[b] from the wave of the sample's first row
+__global__ __launch_bounds__(256) void precond_in_fwd_kernel(long long rows, long long grid_rows, int wz, int wx, int ws, float d2,
+                                                             const float* __restrict__ sigma, const float* __restrict__ z, long long ld_z,
+                                                             const float* __restrict__ x, long long ld_x,
+                                                             const float* __restrict__ stat, long long ld_s, float* __restrict__ out,
+                                                             long long ld_o, float* __restrict__ c_noise) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const long long b = r / grid_rows, g = r - b * grid_rows;
+  const float s = sigma[b], cin = precond_c_in(s, d2);
+  float* o = out + r * ld_o;
+  for (int c = lane; c < wz; c += 64) stg1(o + c, __fmul_rn(cin, ldg1(z + r * ld_z + c)));
+  for (int c = lane; c < wx; c += 64) stg1(o + wz + c, ldg1(x + r * ld_x + c));
+  for (int c = lane; c < ws; c += 64) stg1(o + wz + wx + c, ldg1(stat + g * ld_s + c));
+  if (g == 0 && lane == 0 && c_noise != nullptr) c_noise[b] = __fmul_rn(0.25f, logf(s));
+}
+
+// dz[r] = c_in(sigma_b) dout[r, :wz], dx[r] = dout[r, wz : wz + wx] (each may be NULL)
+__global__ __launch_bounds__(256) void precond_in_bwd_kernel(long long rows, long long grid_rows, int wz, int wx, float d2,
+                                                             const float* __restrict__ sigma, const float* __restrict__ dout,
+                                                             long long ld_do, float* __restrict__ dz, long long ld_dz,
+                                                             float* __restrict__ dx, long long ld_dx) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const float cin = precond_c_in(sigma[r / grid_rows], d2);
+  const float* g = dout + r * ld_do;
+  if (dz != nullptr)
+    for (int c = lane; c < wz; c += 64) stg1(dz + r * ld_dz + c, __fmul_rn(cin, ldg1(g + c)));
+  if (dx != nullptr)
+    for (int c = lane; c < wx; c += 64) stg1(dx + r * ld_dx + c, ldg1(g + wz + c));
+}
+
+// out[r] = c_skip(sigma_b) z[r] + c_out(sigma_b) p[r]
+__global__ __launch_bounds__(256) void precond_out_fwd_kernel(long long rows, long long grid_rows, int width, float d, float d2,
+                                                              const float* __restrict__ sigma, const float* __restrict__ z, long long ld_z,
+                                                              const float* __restrict__ p, long long ld_p, float* __restrict__ out,
+                                                              long long ld_o) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const float s = sigma[r / grid_rows], cs = precond_c_skip(s, d2), co = precond_c_out(s, d, d2);
+  for (int c = lane; c < width; c += 64)
+    stg1(out + r * ld_o + c, __fadd_rn(__fmul_rn(cs, ldg1(z + r * ld_z + c)), __fmul_rn(co, ldg1(p + r * ld_p + c))));
+}
+
+// dz[r] = c_skip(sigma_b) dout[r], dp[r] = c_out(sigma_b) dout[r] (each may be NULL)
+__global__ __launch_bounds__(256) void precond_out_bwd_kernel(long long rows, long long grid_rows, int width, float d, float d2,
+                                                              const float* __restrict__ sigma, const float* __restrict__ dout,
+                                                              long long ld_do, float* __restrict__ dz, long long ld_dz,
+                                                              float* __restrict__ dp, long long ld_dp) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const float s = sigma[r / grid_rows], cs = precond_c_skip(s, d2), co = precond_c_out(s, d, d2);
+  for (int c = lane; c < width; c += 64) {
+    const float g = ldg1(dout + r * ld_do + c);
+    if (dz != nullptr) stg1(dz + r * ld_dz + c, __fmul_rn(cs, g));
+    if (dp != nullptr) stg1(dp + r * ld_dp + c, __fmul_rn(co, g));
+  }
+}
+
+bool precond_ok(int32_t batch, int64_t grid_rows, float sigma_data) {
+  return batch >= 1 && grid_rows >= 1 && (int64_t)batch * grid_rows < ((int64_t)1 << 33) && sigma_data > 0.f;
 }
 
 // ---- beta gate ------------------------------------------------------------------------------------------------------------------
@@ -644,10 +862,13 @@ __global__ __launch_bounds__(256) void fourier_bwd_kernel(long long rows, int F,
   if (lane == 0) dt[r] = s;
 }
 
-int attn_check(const char* bad, int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads, int32_t dim_head) {
-  if (n_dst < 0 || n_src < 0 || n_edges < 0 || heads < 1 || dim_head < 1) return failf(GW_E_BADARG, bad);
+int attn_check(const char* bad, int32_t batch, int64_t e_bstride, int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads,
+               int32_t dim_head) {
+  if (n_dst < 0 || n_src < 0 || n_edges < 0 || heads < 1 || dim_head < 1 || batch < 1) return failf(GW_E_BADARG, bad);
+  if (e_bstride != 0 && e_bstride < n_edges) return failf(GW_E_BADARG, bad);  // the tables of two copies would overlap
   if ((int64_t)heads * dim_head > kMaxRow) return failf(GW_E_UNSUPPORTED, "graph attention: heads * dim_head must be at most 4096");
-  if ((int64_t)n_dst * heads >= ((int64_t)1 << 31) || (int64_t)n_src * heads >= ((int64_t)1 << 31)) return failf(GW_E_BADARG, bad);
+  if ((int64_t)batch * n_dst * heads >= ((int64_t)1 << 31) || (int64_t)batch * n_src * heads >= ((int64_t)1 << 31))
+    return failf(GW_E_BADARG, bad);
   return GW_OK;
 }
 
@@ -655,12 +876,11 @@ int attn_check(const char* bad, int32_t n_dst, int32_t n_src, int32_t n_edges, i
 
 extern "C" {
 
-int gw_graph_attention_forward(int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads, int32_t dim_head, const int32_t* dst_ptr,
-                               const int32_t* src, const int64_t* perm, const float* q, int32_t ld_q, const float* k, int32_t ld_k,
-                               const float* v, int32_t ld_v, const float* e, int32_t ld_e, int32_t mean, float* out, int32_t ld_out,
-                               float* out_heads, int32_t ld_out_heads, float* lse, void* stream) {
-  const char* bad = "gw_graph_attention_forward: bad arguments";
-  if (int rc = attn_check(bad, n_dst, n_src, n_edges, heads, dim_head)) return rc;
+static int attn_forward(const char* bad, int32_t batch, int64_t e_bstride, int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads,
+                        int32_t dim_head, const int32_t* dst_ptr, const int32_t* src, const int64_t* perm, const float* q, int32_t ld_q,
+                        const float* k, int32_t ld_k, const float* v, int32_t ld_v, const float* e, int32_t ld_e, int32_t mean, float* out,
+                        int32_t ld_out, float* out_heads, int32_t ld_out_heads, float* lse, void* stream) {
+  if (int rc = attn_check(bad, batch, e_bstride, n_dst, n_src, n_edges, heads, dim_head)) return rc;
   if (n_dst == 0 || n_edges == 0) return GW_OK;
   const int hc = heads * dim_head;
   if (!dst_ptr || !src || !q || !k || !v || !out || !lse || n_src < 1 || ld_q < hc || ld_k < hc || ld_v < hc || (e && ld_e < hc) ||
@@ -675,7 +895,8 @@ int gw_graph_attention_forward(int32_t n_dst, int32_t n_src, int32_t n_edges, in
   a.q = q, a.k = k, a.v = v, a.e = e, a.ld_q = ld_q, a.ld_k = ld_k, a.ld_v = ld_v, a.ld_e = ld_e;
   a.out = out, a.ld_out = ld_out, a.out_heads = mean ? out_heads : nullptr, a.ld_oh = ld_out_heads, a.lse = lse;
   a.sqrt_c = sqrtf((float)dim_head);
-  const int64_t items = mean ? (int64_t)n_dst : (int64_t)n_dst * heads;
+  a.batch = batch, a.e_bstride = e_bstride, a.planes = (long long)batch * n_dst * heads;
+  const int64_t items = (mean ? (int64_t)n_dst : (int64_t)n_dst * heads) * batch;
   const unsigned grid = (unsigned)((items + 3) / 4);
   const int variant = attn_variant(dim_head, vec);
 #define GW_GC_FWD(NE, VEC, U) hipLaunchKernelGGL((attn_fwd_kernel<NE, VEC, U>), dim3(grid), dim3(256), 0, (hipStream_t)stream, a)
@@ -684,14 +905,30 @@ int gw_graph_attention_forward(int32_t n_dst, int32_t n_src, int32_t n_edges, in
   return check_launch("attn_fwd_kernel launch");
 }
 
-int gw_graph_attention_backward(int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads, int32_t dim_head, const int32_t* dst_ptr,
-                                const int32_t* src, const int32_t* dst, const int64_t* perm, const int32_t* src_pos,
-                                const int32_t* src_ptr, const float* q, int32_t ld_q, const float* k, int32_t ld_k, const float* v,
-                                int32_t ld_v, const float* e, int32_t ld_e, int32_t mean, const float* out_heads, int32_t ld_out_heads,
-                                const float* dout, int32_t ld_dout, const float* lse, float* delta, float* dq, int32_t ld_dq, float* dk,
-                                int32_t ld_dk, float* dv, int32_t ld_dv, float* de, int32_t ld_de, void* stream) {
-  const char* bad = "gw_graph_attention_backward: bad arguments";
-  if (int rc = attn_check(bad, n_dst, n_src, n_edges, heads, dim_head)) return rc;
+int gw_graph_attention_forward(int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads, int32_t dim_head, const int32_t* dst_ptr,
+                               const int32_t* src, const int64_t* perm, const float* q, int32_t ld_q, const float* k, int32_t ld_k,
+                               const float* v, int32_t ld_v, const float* e, int32_t ld_e, int32_t mean, float* out, int32_t ld_out,
+                               float* out_heads, int32_t ld_out_heads, float* lse, void* stream) {
+  return attn_forward("gw_graph_attention_forward: bad arguments", 1, 0, n_dst, n_src, n_edges, heads, dim_head, dst_ptr, src, perm, q,
+                      ld_q, k, ld_k, v, ld_v, e, ld_e, mean, out, ld_out, out_heads, ld_out_heads, lse, stream);
+}
+
+int gw_graph_attention_batched_forward(int32_t batch, int64_t e_batch_stride, int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads,
+                                       int32_t dim_head, const int32_t* dst_ptr, const int32_t* src, const int64_t* perm, const float* q,
+                                       int32_t ld_q, const float* k, int32_t ld_k, const float* v, int32_t ld_v, const float* e, int32_t ld_e,
+                                       int32_t mean, float* out, int32_t ld_out, float* out_heads, int32_t ld_out_heads, float* lse,
+                                       void* stream) {
+  return attn_forward("gw_graph_attention_batched_forward: bad arguments", batch, e_batch_stride, n_dst, n_src, n_edges, heads, dim_head,
+                      dst_ptr, src, perm, q, ld_q, k, ld_k, v, ld_v, e, ld_e, mean, out, ld_out, out_heads, ld_out_heads, lse, stream);
+}
+
+static int attn_backward(const char* bad, int32_t batch, int64_t e_bstride, int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads,
+                         int32_t dim_head, const int32_t* dst_ptr, const int32_t* src, const int32_t* dst, const int64_t* perm,
+                         const int32_t* src_pos, const int32_t* src_ptr, const float* q, int32_t ld_q, const float* k, int32_t ld_k,
+                         const float* v, int32_t ld_v, const float* e, int32_t ld_e, int32_t mean, const float* out_heads,
+                         int32_t ld_out_heads, const float* dout, int32_t ld_dout, const float* lse, float* delta, float* dq, int32_t ld_dq,
+                         float* dk, int32_t ld_dk, float* dv, int32_t ld_dv, float* de, int32_t ld_de, void* stream) {
+  if (int rc = attn_check(bad, batch, e_bstride, n_dst, n_src, n_edges, heads, dim_head)) return rc;
   if (n_edges == 0 || n_dst == 0 || n_src == 0) return GW_OK;
   const int hc = heads * dim_head;
   if (!dst_ptr || !src || !dst || !src_pos || !src_ptr || !q || !k || !v || !out_heads || !dout || !lse || !delta || !dq || !dk || !dv ||
@@ -710,18 +947,50 @@ int gw_graph_attention_backward(int32_t n_dst, int32_t n_src, int32_t n_edges, i
   a.dout = dout, a.ld_dout = ld_dout, a.delta = delta;
   a.dq = dq, a.dk = dk, a.dv = dv, a.de = de, a.ld_dq = ld_dq, a.ld_dk = ld_dk, a.ld_dv = ld_dv, a.ld_de = ld_de;
   a.sqrt_c = sqrtf((float)dim_head);
+  a.batch = batch, a.e_bstride = e_bstride, a.planes = (long long)batch * n_dst * heads;
+  a.de_loop = (de != nullptr && batch > 1 && e_bstride == 0) ? 1 : 0;  // one de table for every copy: summed by the owning wave
   const int variant = attn_variant(dim_head, vec);
-  const unsigned grid_d = (unsigned)(((int64_t)n_dst * heads + 3) / 4), grid_s = (unsigned)(((int64_t)n_src * heads + 3) / 4);
-#define GW_GC_BWD_DST(NE, VEC, U) hipLaunchKernelGGL((attn_bwd_dst_kernel<NE, VEC>), dim3(grid_d), dim3(256), 0, (hipStream_t)stream, a)
-  GW_GC_VARIANTS(GW_GC_BWD_DST, hipLaunchKernelGGL(attn_bwd_dst_long_kernel, dim3((unsigned)((int64_t)n_dst * heads)), dim3(64), 0,
-                                                   (hipStream_t)stream, a))
+  const int64_t items_d = (int64_t)n_dst * heads * (a.de_loop ? 1 : batch), items_s = (int64_t)n_src * heads * batch;
+  const unsigned grid_d = (unsigned)((items_d + 3) / 4), grid_s = (unsigned)((items_s + 3) / 4);
+#define GW_GC_BWD_DST(NE, VEC, U)                                                                                      \
+  if (a.de_loop)                                                                                                       \
+    hipLaunchKernelGGL((attn_bwd_dst_kernel<NE, VEC, true>), dim3(grid_d), dim3(256), 0, (hipStream_t)stream, a);       \
+  else                                                                                                                 \
+    hipLaunchKernelGGL((attn_bwd_dst_kernel<NE, VEC, false>), dim3(grid_d), dim3(256), 0, (hipStream_t)stream, a)
+  GW_GC_VARIANTS(GW_GC_BWD_DST, if (a.de_loop) hipLaunchKernelGGL(attn_bwd_dst_long_kernel<true>, dim3((unsigned)items_d), dim3(64), 0,
+                                                                   (hipStream_t)stream, a);
+                                else hipLaunchKernelGGL(attn_bwd_dst_long_kernel<false>, dim3((unsigned)items_d), dim3(64), 0,
+                                                        (hipStream_t)stream, a))
 #undef GW_GC_BWD_DST
   if (int rc = check_launch("attn_bwd_dst_kernel launch")) return rc;
 #define GW_GC_BWD_SRC(NE, VEC, U) hipLaunchKernelGGL((attn_bwd_src_kernel<NE, VEC>), dim3(grid_s), dim3(256), 0, (hipStream_t)stream, a)
-  GW_GC_VARIANTS(GW_GC_BWD_SRC, hipLaunchKernelGGL(attn_bwd_src_long_kernel, dim3((unsigned)((int64_t)n_src * heads)), dim3(64), 0,
+  GW_GC_VARIANTS(GW_GC_BWD_SRC, hipLaunchKernelGGL(attn_bwd_src_long_kernel, dim3((unsigned)items_s), dim3(64), 0,
                                                    (hipStream_t)stream, a))
 #undef GW_GC_BWD_SRC
   return check_launch("attn_bwd_src_kernel launch");
+}
+
+int gw_graph_attention_backward(int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads, int32_t dim_head, const int32_t* dst_ptr,
+                                const int32_t* src, const int32_t* dst, const int64_t* perm, const int32_t* src_pos,
+                                const int32_t* src_ptr, const float* q, int32_t ld_q, const float* k, int32_t ld_k, const float* v,
+                                int32_t ld_v, const float* e, int32_t ld_e, int32_t mean, const float* out_heads, int32_t ld_out_heads,
+                                const float* dout, int32_t ld_dout, const float* lse, float* delta, float* dq, int32_t ld_dq, float* dk,
+                                int32_t ld_dk, float* dv, int32_t ld_dv, float* de, int32_t ld_de, void* stream) {
+  return attn_backward("gw_graph_attention_backward: bad arguments", 1, 0, n_dst, n_src, n_edges, heads, dim_head, dst_ptr, src, dst, perm,
+                       src_pos, src_ptr, q, ld_q, k, ld_k, v, ld_v, e, ld_e, mean, out_heads, ld_out_heads, dout, ld_dout, lse, delta, dq,
+                       ld_dq, dk, ld_dk, dv, ld_dv, de, ld_de, stream);
+}
+
+int gw_graph_attention_batched_backward(int32_t batch, int64_t e_batch_stride, int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads,
+                                        int32_t dim_head, const int32_t* dst_ptr, const int32_t* src, const int32_t* dst,
+                                        const int64_t* perm, const int32_t* src_pos, const int32_t* src_ptr, const float* q, int32_t ld_q,
+                                        const float* k, int32_t ld_k, const float* v, int32_t ld_v, const float* e, int32_t ld_e,
+                                        int32_t mean, const float* out_heads, int32_t ld_out_heads, const float* dout, int32_t ld_dout,
+                                        const float* lse, float* delta, float* dq, int32_t ld_dq, float* dk, int32_t ld_dk, float* dv,
+                                        int32_t ld_dv, float* de, int32_t ld_de, void* stream) {
+  return attn_backward("gw_graph_attention_batched_backward: bad arguments", batch, e_batch_stride, n_dst, n_src, n_edges, heads, dim_head,
+                       dst_ptr, src, dst, perm, src_pos, src_ptr, q, ld_q, k, ld_k, v, ld_v, e, ld_e, mean, out_heads, ld_out_heads, dout,
+                       ld_dout, lse, delta, dq, ld_dq, dk, ld_dk, dv, ld_dv, de, ld_de, stream);
 }
 
 int gw_cond_layernorm_forward(int64_t rows, int32_t width, int32_t act, const float* x, int32_t ld_x, const float* scale, int32_t ld_scale,
@@ -731,7 +1000,7 @@ int gw_cond_layernorm_forward(int64_t rows, int32_t width, int32_t act, const fl
     return failf(GW_E_BADARG, "gw_cond_layernorm_forward: bad arguments");
   if (rows == 0) return GW_OK;
   hipLaunchKernelGGL(cln_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (long long)rows, (int)width,
-                     (int)act, x, (long long)ld_x, scale, (long long)ld_scale, bias, (long long)ld_bias, out, (long long)ld_out);
+                     (int)act, x, (long long)ld_x, scale, (long long)ld_scale, bias, (long long)ld_bias, out, (long long)ld_out, 1LL);
   return check_launch("cln_fwd_kernel launch");
 }
 
@@ -745,8 +1014,113 @@ int gw_cond_layernorm_backward(int64_t rows, int32_t width, int32_t act, const f
   if (rows == 0) return GW_OK;
   hipLaunchKernelGGL(cln_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (long long)rows, (int)width,
                      (int)act, x, (long long)ld_x, scale, (long long)ld_scale, bias, (long long)ld_bias, dout, (long long)ld_dout, dx,
-                     (long long)ld_dx, dscale, dbias, (long long)ld_dsb);
+                     (long long)ld_dx, dscale, dbias, (long long)ld_dsb, 1LL, (float*)nullptr);
   return check_launch("cln_bwd_kernel launch");
+}
+
+int gw_cond_layernorm_grouped_forward(int64_t rows, int32_t width, int32_t act, int64_t rows_per_group, const float* x, int32_t ld_x,
+                                      const float* scale, int32_t ld_scale, const float* bias, int32_t ld_bias, float* out, int32_t ld_out,
+                                      void* stream) {
+  if (!x || !scale || !bias || !out || !cln_grouped_ok(rows, width, rows_per_group) || act < GW_ACT_NONE || act > GW_ACT_SILU ||
+      ld_x < width || ld_scale < width || ld_bias < width || ld_out < width)
+    return failf(GW_E_BADARG, "gw_cond_layernorm_grouped_forward: bad arguments");
+  if (rows == 0) return GW_OK;
+  hipLaunchKernelGGL(cln_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (long long)rows, (int)width,
+                     (int)act, x, (long long)ld_x, scale, (long long)ld_scale, bias, (long long)ld_bias, out, (long long)ld_out,
+                     (long long)rows_per_group);
+  return check_launch("cln_fwd_kernel launch");
+}
+
+size_t gw_cond_layernorm_grouped_workspace_bytes(int64_t rows, int32_t width, int64_t rows_per_group) {
+  if (!cln_grouped_ok(rows, width, rows_per_group) || rows < 1) {
+    failf(GW_E_BADARG, "gw_cond_layernorm_grouped_workspace_bytes: bad arguments");
+    return 0;
+  }
+  return cln_grouped_bytes(rows, width, rows_per_group);
+}
+
+int gw_cond_layernorm_grouped_backward(int64_t rows, int32_t width, int32_t act, int64_t rows_per_group, const float* x, int32_t ld_x,
+                                       const float* scale, int32_t ld_scale, const float* bias, int32_t ld_bias, const float* dout,
+                                       int32_t ld_dout, void* workspace, size_t workspace_bytes, float* dx, int32_t ld_dx, float* dscale,
+                                       float* dbias, int32_t ld_dsb, void* stream) {
+  const char* bad = "gw_cond_layernorm_grouped_backward: bad arguments";
+  if (!x || !scale || !bias || !dout || !workspace || (!dx && !dscale && !dbias) || !cln_grouped_ok(rows, width, rows_per_group) ||
+      act < GW_ACT_NONE || act > GW_ACT_SILU || ld_x < width || ld_scale < width || ld_bias < width || ld_dout < width ||
+      (dx && ld_dx < width) || ((dscale || dbias) && ld_dsb < width))
+    return failf(GW_E_BADARG, bad);
+  if (rows == 0) return GW_OK;
+  if (workspace_bytes < cln_grouped_bytes(rows, width, rows_per_group))
+    return failf(GW_E_BADARG, "gw_cond_layernorm_grouped_backward: bad arguments (workspace)");
+  float* stats = (float*)workspace;
+  float* part = stats + 2 * rows;
+  hipStream_t st = (hipStream_t)stream;
+  // (with dx NULL the row kernel still leaves the statistics the column pass reads)
+  hipLaunchKernelGGL(cln_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, (long long)rows, (int)width, (int)act, x,
+                     (long long)ld_x, scale, (long long)ld_scale, bias, (long long)ld_bias, dout, (long long)ld_dout, dx, (long long)ld_dx,
+                     (float*)nullptr, (float*)nullptr, (long long)ld_dsb, (long long)rows_per_group, stats);
+  if (int rc = check_launch("cln_bwd_kernel launch")) return rc;
+  if (!dscale && !dbias) return GW_OK;
+  const int64_t groups = (rows + rows_per_group - 1) / rows_per_group;
+  // slabs of the longest group (a shorter last group leaves its later slabs empty: zero partials)
+  const int slabs = (int)(((rows_per_group < rows ? rows_per_group : rows) + kGateSlab - 1) / kGateSlab);
+  hipLaunchKernelGGL(cln_cols_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)slabs, (unsigned)groups), dim3(256), 0, st,
+                     (long long)rows, (int)width, (int)act, (long long)rows_per_group, x, (long long)ld_x, scale, (long long)ld_scale, bias,
+                     (long long)ld_bias, dout, (long long)ld_dout, (const float*)stats, part);
+  if (int rc = check_launch("cln_cols_kernel launch")) return rc;
+  hipLaunchKernelGGL(cln_sum_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)groups), dim3(256), 0, st, slabs, (int)width,
+                     (const float*)part, dscale, dbias, (long long)ld_dsb);
+  return check_launch("cln_sum_kernel launch");
+}
+
+int gw_gencast_precond_input_forward(int32_t batch, int64_t grid_rows, int32_t w_z, int32_t w_x, int32_t w_s, float sigma_data,
+                                     const float* sigma, const float* z, int32_t ld_z, const float* x, int32_t ld_x, const float* stat,
+                                     int32_t ld_stat, float* out, int32_t ld_out, float* c_noise, void* stream) {
+  if (!precond_ok(batch, grid_rows, sigma_data) || !sigma || !out || w_z < 0 || w_x < 0 || w_s < 0 || (w_z && (!z || ld_z < w_z)) ||
+      (w_x && (!x || ld_x < w_x)) || (w_s && (!stat || ld_stat < w_s)) || (int64_t)w_z + w_x + w_s < 1 || ld_out < (int64_t)w_z + w_x + w_s)
+    return failf(GW_E_BADARG, "gw_gencast_precond_input_forward: bad arguments");
+  const long long rows = (long long)batch * grid_rows;
+  hipLaunchKernelGGL(precond_in_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows, (long long)grid_rows,
+                     (int)w_z, (int)w_x, (int)w_s, (float)((double)sigma_data * sigma_data), sigma, z, (long long)ld_z, x, (long long)ld_x, stat,
+                     (long long)ld_stat, out, (long long)ld_out, c_noise);
+  return check_launch("precond_in_fwd_kernel launch");
+}
+
+int gw_gencast_precond_input_backward(int32_t batch, int64_t grid_rows, int32_t w_z, int32_t w_x, float sigma_data, const float* sigma,
+                                      const float* dout, int32_t ld_dout, float* dz, int32_t ld_dz, float* dx, int32_t ld_dx,
+                                      void* stream) {
+  if (!precond_ok(batch, grid_rows, sigma_data) || !sigma || !dout || (!dz && !dx) || w_z < 0 || w_x < 0 || ld_dout < (int64_t)w_z + w_x ||
+      (dz && ld_dz < w_z) || (dx && ld_dx < w_x))
+    return failf(GW_E_BADARG, "gw_gencast_precond_input_backward: bad arguments");
+  const long long rows = (long long)batch * grid_rows;
+  hipLaunchKernelGGL(precond_in_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows, (long long)grid_rows,
+                     (int)w_z, (int)w_x, (float)((double)sigma_data * sigma_data), sigma, dout, (long long)ld_dout, dz, (long long)ld_dz, dx,
+                     (long long)ld_dx);
+  return check_launch("precond_in_bwd_kernel launch");
+}
+
+int gw_gencast_precond_output_forward(int32_t batch, int64_t grid_rows, int32_t width, float sigma_data, const float* sigma, const float* z,
+                                      int32_t ld_z, const float* preds, int32_t ld_preds, float* out, int32_t ld_out, void* stream) {
+  if (!precond_ok(batch, grid_rows, sigma_data) || !sigma || !z || !preds || !out || width < 1 || ld_z < width || ld_preds < width ||
+      ld_out < width)
+    return failf(GW_E_BADARG, "gw_gencast_precond_output_forward: bad arguments");
+  const long long rows = (long long)batch * grid_rows;
+  hipLaunchKernelGGL(precond_out_fwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows,
+                     (long long)grid_rows, (int)width, sigma_data, (float)((double)sigma_data * sigma_data), sigma, z, (long long)ld_z, preds,
+                     (long long)ld_preds, out, (long long)ld_out);
+  return check_launch("precond_out_fwd_kernel launch");
+}
+
+int gw_gencast_precond_output_backward(int32_t batch, int64_t grid_rows, int32_t width, float sigma_data, const float* sigma,
+                                       const float* dout, int32_t ld_dout, float* dz, int32_t ld_dz, float* dpreds, int32_t ld_dpreds,
+                                       void* stream) {
+  if (!precond_ok(batch, grid_rows, sigma_data) || !sigma || !dout || (!dz && !dpreds) || width < 1 || ld_dout < width ||
+      (dz && ld_dz < width) || (dpreds && ld_dpreds < width))
+    return failf(GW_E_BADARG, "gw_gencast_precond_output_backward: bad arguments");
+  const long long rows = (long long)batch * grid_rows;
+  hipLaunchKernelGGL(precond_out_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows,
+                     (long long)grid_rows, (int)width, sigma_data, (float)((double)sigma_data * sigma_data), sigma, dout, (long long)ld_dout, dz,
+                     (long long)ld_dz, dpreds, (long long)ld_dpreds);
+  return check_launch("precond_out_bwd_kernel launch");
 }
 
 int gw_beta_gate_forward(int64_t rows, int32_t width, const float* out, int32_t ld_out, const float* x_r, int32_t ld_xr, const float* w,

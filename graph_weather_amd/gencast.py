@@ -18,6 +18,12 @@ node-level products gathered in the epilogue of the edge-level product (``gw_lin
 
 ``edge_index`` arrives per call ([2, E] int64 COO, any order, duplicates are separate edges); it is sorted by destination once
 per tensor and cached on (address, shape, version).  fp32 only, no dropout, no bf16 modes; there is no CPU path.
+
+Batch-shared form (what ``gencast_model.Denoiser`` runs): the reference batches by replicating the graph - B disconnected copies,
+``edge_index`` and ``edge_attr`` concatenated B times - so every product on edge attributes alone and every conditioning row is
+computed B times over.  ``Encoder._forward_shared``, ``Processor._forward_shared`` and ``Decoder._forward_shared`` take ONE graph
+and node rows [B n, .]: the attention, ConditionalLayerNorm and gather kernels index copy b's node rows at b n and read one edge
+table, one plan and one conditioning row per sample.  The public ``forward``s are unchanged.
 """
 from __future__ import annotations
 
@@ -39,7 +45,10 @@ from .wide import _Add, _L, _ld, _rows, _st, add_rows, linear_forward, linear_ga
 __all__ = ["MLP", "InteractionNetwork", "FourierEmbedding", "ConditionalLayerNorm", "CondTransformerBlock", "TransformerConv",
            "Encoder", "Processor", "Decoder", "EdgePlan", "edge_plan", "graph_attention_forward", "graph_attention_backward",
            "cond_layernorm_forward", "cond_layernorm_backward", "beta_gate_forward", "beta_gate_backward", "silu_forward",
-           "silu_backward", "fourier_forward", "fourier_backward"]
+           "silu_backward", "fourier_forward", "fourier_backward", "graph_attention_batched_forward",
+           "graph_attention_batched_backward", "edge_table_stride", "cond_layernorm_grouped_forward",
+           "cond_layernorm_grouped_backward", "precond_input_forward", "precond_input_backward", "precond_output_forward",
+           "precond_output_backward"]
 
 MAX_ROW = 4096  # heads * dim_head of the graph attention kernels
 
@@ -273,6 +282,191 @@ def fourier_backward(t: torch.Tensor, dout: torch.Tensor, num_frequencies: int, 
     return dt
 
 
+# ---- batch-shared forms -------------------------------------------------------------------------------------------------
+def edge_table_stride(e_rows: Optional[int], num_edges: int, batch: int) -> int:
+    """The rows between two copies' edge tables for a table of ``e_rows`` rows (None: no table): 0 - one table [E, .] read by
+    every copy - or E - one table per copy, [batch E, .].  With one copy the two coincide (0)."""
+    if e_rows is None or e_rows == num_edges:
+        return 0
+    if e_rows == batch * num_edges:
+        return num_edges
+    raise RuntimeError("graph_weather_amd: batch-shared graph attention takes edge features with %d rows (shared) or %d (one table "
+                       "per copy), got %d" % (num_edges, batch * num_edges, e_rows))
+
+
+def graph_attention_batched_forward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, e: Optional[torch.Tensor], plan: GraphPlan,
+                                    heads: int, mean: bool, batch: int, keep_heads: bool = True):
+    """``graph_attention_forward`` on ``batch`` copies of the plan's graph (include/gw_amd.h: gw_graph_attention_batched_forward):
+    q [batch n_dst, H C], k, v [batch n_src, H C]; e [E, H C] shared by the copies, [batch E, H C] one table per copy, or None ->
+    (out, per-head rows, lse [2, batch n_dst H])."""
+    q, k, v = _rows(q, "q"), _rows(k, "k"), _rows(v, "v")
+    hc = int(q.shape[1])
+    if batch < 1 or hc % heads:
+        raise RuntimeError("graph_weather_amd: batch-shared graph attention needs batch >= 1 and a width of q (%d) that is a multiple "
+                           "of the heads (%d)" % (hc, heads))
+    C = hc // heads
+    _check_attention(heads, C)
+    E, nd, ns = plan.num_edges, plan.n_dst, plan.n_src
+    if tuple(q.shape) != (batch * nd, hc) or tuple(k.shape) != (batch * ns, hc) or tuple(v.shape) != (batch * ns, hc):
+        raise RuntimeError("graph_weather_amd: batch-shared graph attention expects q [%d, %d] and k, v [%d, %d], got %s, %s, %s"
+                           % (batch * nd, hc, batch * ns, hc, tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    if e is not None:
+        e = _rows(e, "edge features")
+        if int(e.shape[1]) != hc:
+            raise RuntimeError("graph_weather_amd: graph attention expects edge features %d wide, got %d" % (hc, int(e.shape[1])))
+    stride = edge_table_stride(None if e is None else int(e.shape[0]), E, batch)
+    new = torch.zeros if E == 0 else torch.empty
+    out = new((batch * nd, C if mean else hc), dtype=torch.float32, device=q.device)
+    out_heads = new((batch * nd, hc), dtype=torch.float32, device=q.device) if (mean and keep_heads) else None
+    lse = new((2, batch * nd * heads), dtype=torch.float32, device=q.device)
+    with on_device_of(out):
+        _lib.check(_L().gw_graph_attention_batched_forward(
+            batch, stride, nd, ns, E, heads, C, plan.dst_ptr().data_ptr(), plan.src.data_ptr(), plan.perm.data_ptr(), q.data_ptr(),
+            _ld(q), k.data_ptr(), _ld(k), v.data_ptr(), _ld(v), _p(e), 0 if e is None else _ld(e), 1 if mean else 0, out.data_ptr(),
+            _ld(out), _p(out_heads), hc, lse.data_ptr(), _st(out)), "gw_graph_attention_batched_forward")
+    return out, (out_heads if mean else out), lse
+
+
+def graph_attention_batched_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, e: Optional[torch.Tensor], plan: GraphPlan,
+                                     heads: int, mean: bool, batch: int, out_heads: torch.Tensor, lse: torch.Tensor,
+                                     dout: torch.Tensor, want_de: bool = True):
+    """(dq, dk, dv, de or None) of ``graph_attention_batched_forward``; de is shaped like e - for a shared table the sum over the
+    copies in copy order."""
+    q, k, v, out_heads, dout = _rows(q, "q"), _rows(k, "k"), _rows(v, "v"), _rows(out_heads, "out"), _rows(dout, "dout")
+    hc = int(q.shape[1])
+    C = hc // heads
+    E, nd, ns = plan.num_edges, plan.n_dst, plan.n_src
+    if e is not None:
+        e = _rows(e, "edge features")
+    stride = edge_table_stride(None if e is None else int(e.shape[0]), E, batch)
+    new = torch.zeros if E == 0 else torch.empty
+    dq = new((batch * nd, hc), dtype=torch.float32, device=q.device)
+    dk, dv = (new((batch * ns, hc), dtype=torch.float32, device=q.device) for _ in range(2))
+    de = new((int(e.shape[0]), hc), dtype=torch.float32, device=q.device) if (e is not None and want_de) else None
+    delta = torch.empty((max(batch * nd * heads, 1),), dtype=torch.float32, device=q.device)
+    src_pos, src_ptr = plan.src_sorted()
+    with on_device_of(dq):
+        _lib.check(_L().gw_graph_attention_batched_backward(
+            batch, stride, nd, ns, E, heads, C, plan.dst_ptr().data_ptr(), plan.src.data_ptr(), plan.dst.data_ptr(),
+            plan.perm.data_ptr(), src_pos.data_ptr(), src_ptr.data_ptr(), q.data_ptr(), _ld(q), k.data_ptr(), _ld(k), v.data_ptr(),
+            _ld(v), _p(e), 0 if e is None else _ld(e), 1 if mean else 0, out_heads.data_ptr(), _ld(out_heads), dout.data_ptr(),
+            _ld(dout), lse.data_ptr(), delta.data_ptr(), dq.data_ptr(), hc, dk.data_ptr(), hc, dv.data_ptr(), hc, _p(de), hc, _st(dq)),
+            "gw_graph_attention_batched_backward")
+    return dq, dk, dv, de
+
+
+def _group_rows(x: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, rows_per_group: int) -> int:
+    rows, width = int(x.shape[0]), int(x.shape[1])
+    groups = -(-rows // rows_per_group) if rows_per_group >= 1 else -1
+    if rows_per_group < 1 or tuple(scale.shape) != (groups, width) or tuple(bias.shape) != (groups, width):
+        raise RuntimeError("graph_weather_amd: %d rows in groups of %d need scale and bias [%d, %d], got %s and %s"
+                           % (rows, rows_per_group, groups, width, tuple(scale.shape), tuple(bias.shape)))
+    return groups
+
+
+def cond_layernorm_grouped_forward(x: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, rows_per_group: int,
+                                   act: Optional[str] = None) -> torch.Tensor:
+    """``cond_layernorm_forward`` with one scale and bias row per ``rows_per_group`` consecutive rows of x."""
+    x, scale, bias = _rows(x, "x"), _rows(scale, "scale"), _rows(bias, "bias")
+    _group_rows(x, scale, bias, rows_per_group)
+    rows, width = int(x.shape[0]), int(x.shape[1])
+    out = torch.empty((rows, width), dtype=torch.float32, device=x.device)
+    with on_device_of(out):
+        _lib.check(_L().gw_cond_layernorm_grouped_forward(rows, width, _ACT_CODE[act], rows_per_group, x.data_ptr(), _ld(x),
+                                                          scale.data_ptr(), _ld(scale), bias.data_ptr(), _ld(bias), out.data_ptr(), width,
+                                                          _st(out)), "gw_cond_layernorm_grouped_forward")
+    return out
+
+
+def cond_layernorm_grouped_backward(x: torch.Tensor, scale: torch.Tensor, bias: torch.Tensor, rows_per_group: int, act: Optional[str],
+                                    dout: torch.Tensor):
+    """(dx, dscale [groups, width], dbias [groups, width]) of ``cond_layernorm_grouped_forward``."""
+    x, scale, bias, dout = _rows(x, "x"), _rows(scale, "scale"), _rows(bias, "bias"), _rows(dout, "dout")
+    groups = _group_rows(x, scale, bias, rows_per_group)
+    rows, width = int(x.shape[0]), int(x.shape[1])
+    dx = torch.empty((rows, width), dtype=torch.float32, device=x.device)
+    dscale, dbias = (torch.zeros((groups, width), dtype=torch.float32, device=x.device) for _ in range(2))
+    if rows:
+        nbytes = int(_L().gw_cond_layernorm_grouped_workspace_bytes(rows, width, rows_per_group))
+        ws = _workspace(nbytes, "gw_cond_layernorm_grouped_workspace_bytes", x.device)
+        with on_device_of(dx):
+            _lib.check(_L().gw_cond_layernorm_grouped_backward(rows, width, _ACT_CODE[act], rows_per_group, x.data_ptr(), _ld(x),
+                                                               scale.data_ptr(), _ld(scale), bias.data_ptr(), _ld(bias), dout.data_ptr(),
+                                                               _ld(dout), ws.data_ptr(), nbytes, dx.data_ptr(), width, dscale.data_ptr(),
+                                                               dbias.data_ptr(), width, _st(dx)), "gw_cond_layernorm_grouped_backward")
+    return dx, dscale, dbias
+
+
+def _sigma_rows(sigma: torch.Tensor, rows: int, what: str):
+    _need_hip(sigma, "noise_levels")
+    sigma = sigma.reshape(-1).contiguous()
+    batch = int(sigma.numel())
+    if sigma.dtype != torch.float32 or batch < 1 or rows % batch:
+        raise RuntimeError("graph_weather_amd: %s needs float32 noise levels, one per sample, and rows that split evenly among them "
+                           "(%d rows, %d levels)" % (what, rows, batch))
+    return sigma, batch, rows // batch
+
+
+def precond_input_forward(z: torch.Tensor, x: torch.Tensor, sigma: torch.Tensor, static: torch.Tensor, sigma_data: float = 1.0):
+    """The encoder's grid input rows and the scaled noise levels: (c_in(sigma_b) z | x | static[g]) for row b G + g, z [B G, wz],
+    x [B G, wx], static [G, ws], sigma [B] or [B, 1] -> ([B G, wz + wx + ws], c_noise [B, 1])."""
+    z, x, static = _rows(z, "corrupted targets"), _rows(x, "previous inputs"), _rows(static, "static grid features")
+    sigma, batch, G = _sigma_rows(sigma, int(z.shape[0]), "the input preconditioning")
+    if int(x.shape[0]) != batch * G or int(static.shape[0]) != G:
+        raise RuntimeError("graph_weather_amd: the input preconditioning expects %d rows of previous inputs and %d static rows, got %d "
+                           "and %d" % (batch * G, G, int(x.shape[0]), int(static.shape[0])))
+    wz, wx, ws = int(z.shape[1]), int(x.shape[1]), int(static.shape[1])
+    out = torch.empty((batch * G, wz + wx + ws), dtype=torch.float32, device=z.device)
+    c_noise = torch.empty((batch, 1), dtype=torch.float32, device=z.device)
+    with on_device_of(out):
+        _lib.check(_L().gw_gencast_precond_input_forward(batch, G, wz, wx, ws, float(sigma_data), sigma.data_ptr(), z.data_ptr(), _ld(z),
+                                                         x.data_ptr(), _ld(x), static.data_ptr(), _ld(static), out.data_ptr(),
+                                                         wz + wx + ws, c_noise.data_ptr(), _st(out)), "gw_gencast_precond_input_forward")
+    return out, c_noise
+
+
+def precond_input_backward(dout: torch.Tensor, sigma: torch.Tensor, wz: int, wx: int, sigma_data: float = 1.0):
+    """(dz, dx) of ``precond_input_forward``."""
+    dout = _rows(dout, "dout")
+    sigma, batch, G = _sigma_rows(sigma, int(dout.shape[0]), "the input preconditioning")
+    dz = torch.empty((batch * G, wz), dtype=torch.float32, device=dout.device)
+    dx = torch.empty((batch * G, wx), dtype=torch.float32, device=dout.device)
+    with on_device_of(dz):
+        _lib.check(_L().gw_gencast_precond_input_backward(batch, G, wz, wx, float(sigma_data), sigma.data_ptr(), dout.data_ptr(), _ld(dout),
+                                                          dz.data_ptr(), wz, dx.data_ptr(), wx, _st(dz)),
+                   "gw_gencast_precond_input_backward")
+    return dz, dx
+
+
+def precond_output_forward(z: torch.Tensor, preds: torch.Tensor, sigma: torch.Tensor, sigma_data: float = 1.0) -> torch.Tensor:
+    """c_skip(sigma_b) z + c_out(sigma_b) preds on rows b G + g."""
+    z, preds = _rows(z, "corrupted targets"), _rows(preds, "predictions")
+    sigma, batch, G = _sigma_rows(sigma, int(z.shape[0]), "the output preconditioning")
+    if z.shape != preds.shape:
+        raise RuntimeError("graph_weather_amd: the output preconditioning expects predictions shaped like the targets %s, got %s"
+                           % (tuple(z.shape), tuple(preds.shape)))
+    width = int(z.shape[1])
+    out = torch.empty((batch * G, width), dtype=torch.float32, device=z.device)
+    with on_device_of(out):
+        _lib.check(_L().gw_gencast_precond_output_forward(batch, G, width, float(sigma_data), sigma.data_ptr(), z.data_ptr(), _ld(z),
+                                                          preds.data_ptr(), _ld(preds), out.data_ptr(), width, _st(out)),
+                   "gw_gencast_precond_output_forward")
+    return out
+
+
+def precond_output_backward(dout: torch.Tensor, sigma: torch.Tensor, sigma_data: float = 1.0):
+    """(dz, dpreds) of ``precond_output_forward``."""
+    dout = _rows(dout, "dout")
+    sigma, batch, G = _sigma_rows(sigma, int(dout.shape[0]), "the output preconditioning")
+    width = int(dout.shape[1])
+    dz, dp = (torch.empty((batch * G, width), dtype=torch.float32, device=dout.device) for _ in range(2))
+    with on_device_of(dz):
+        _lib.check(_L().gw_gencast_precond_output_backward(batch, G, width, float(sigma_data), sigma.data_ptr(), dout.data_ptr(), _ld(dout),
+                                                           dz.data_ptr(), width, dp.data_ptr(), width, _st(dz)),
+                   "gw_gencast_precond_output_backward")
+    return dz, dp
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # autograd nodes
 # ---------------------------------------------------------------------------------------------------------------------
@@ -436,6 +630,117 @@ class _SegmentSum(Function):
         return gather_rows(dout.contiguous(), ep.n_dst, ep.dst32, 1, ep.num_edges), None
 
 
+class _GraphAttentionBatched(Function):
+    @staticmethod
+    def forward(ctx, q, k, v, e, plan: GraphPlan, heads: int, mean: bool, batch: int):
+        need = any(ctx.needs_input_grad[:4])
+        out, out_heads, lse = graph_attention_batched_forward(q, k, v, e, plan, heads, mean, batch, keep_heads=need)
+        ctx.plan, ctx.heads, ctx.mean, ctx.batch = plan, heads, mean, batch
+        ctx.save_for_backward(q, k, v, e, out_heads, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, e, out_heads, lse = ctx.saved_tensors
+        dq, dk, dv, de = graph_attention_batched_backward(q, k, v, e, ctx.plan, ctx.heads, ctx.mean, ctx.batch, out_heads, lse, dout,
+                                                          want_de=e is not None and ctx.needs_input_grad[3])
+        return dq, dk, dv, de, None, None, None, None
+
+
+class _CondLayerNormGrouped(Function):
+    @staticmethod
+    def forward(ctx, x, scale, bias, rows_per_group: int, act):
+        ctx.act, ctx.rpg = act, rows_per_group
+        ctx.save_for_backward(x, scale, bias)
+        return cond_layernorm_grouped_forward(x, scale, bias, rows_per_group, act)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, scale, bias = ctx.saved_tensors
+        return cond_layernorm_grouped_backward(x, scale, bias, ctx.rpg, ctx.act, dout) + (None, None)
+
+
+class _PrecondInput(Function):
+    @staticmethod
+    def forward(ctx, z, x, sigma, static, sigma_data: float):
+        out, c_noise = precond_input_forward(z, x, sigma, static, sigma_data)
+        ctx.meta = (int(z.shape[1]), int(x.shape[1]), sigma_data)
+        ctx.save_for_backward(sigma)
+        ctx.mark_non_differentiable(c_noise)
+        return out, c_noise
+
+    @staticmethod
+    def backward(ctx, dout, _):
+        (sigma,) = ctx.saved_tensors
+        dz, dx = precond_input_backward(dout, sigma, *ctx.meta)
+        return dz, dx, None, None, None
+
+
+class _PrecondOutput(Function):
+    @staticmethod
+    def forward(ctx, z, preds, sigma, sigma_data: float):
+        ctx.sigma_data = sigma_data
+        ctx.save_for_backward(sigma)
+        return precond_output_forward(z, preds, sigma, sigma_data)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (sigma,) = ctx.saved_tensors
+        dz, dp = precond_output_backward(dout, sigma, ctx.sigma_data)
+        return dz, dp, None, None
+
+
+class _LinearGatherShared(Function):
+    """``_LinearGather`` on ``batch`` copies of one graph: row m = (b, r) = divmod(m, rows_per_batch) of the output is
+    x[m] @ w.T + b + sum_i table_i[b rows_pb_i + idx_i[r]] (x, w None: no product).  ``meta[i]`` = (idx or None, rows_pb, (perm,
+    ptr)): rows_pb 0 is a table shared by the copies, whose gradient sums over the copies too (``gw_segment_sum_rows_wide`` with one
+    output batch: one fixed order); (perm, ptr) the CSR that groups the rows r by table row (identity idx: perm None, ptr 0..n)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, meta, batch: int, rows_per_batch: int, *tables):
+        rows = batch * rows_per_batch
+        out = linear_gather_forward(x, w, b, False, [(t, m[0], m[1]) for t, m in zip(tables, meta)], rows, max(rows_per_batch, 1))
+        ctx.meta, ctx.has_b, ctx.batch, ctx.rpb = meta, b is not None, batch, rows_per_batch
+        ctx.save_for_backward(x, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w = ctx.saved_tensors
+        dz = _rows(dout, "dout")
+        dx = dw = db = None
+        if w is not None:
+            if ctx.needs_input_grad[0]:
+                dx = linear_forward(dz, w.detach().t().contiguous(), None, False)
+            if ctx.needs_input_grad[1] or (ctx.has_b and ctx.needs_input_grad[2]):
+                dw, db = gemm_tn_ordered(dz, x, ctx.has_b)
+        dts = []
+        for i, (idx, rows_pb, (perm, ptr)) in enumerate(ctx.meta):
+            if not ctx.needs_input_grad[6 + i]:
+                dts.append(None)
+            elif idx is None and rows_pb:
+                dts.append(dz)
+            else:
+                dts.append(segment_sum_rows(dz, ctx.rpb, ctx.batch, ctx.batch if rows_pb else 1, int(ptr.numel()) - 1, ptr, perm))
+        return (dx, dw, db, None, None, None, *dts)
+
+
+class _SegmentSumShared(Function):
+    """``_SegmentSum`` per copy: rows [batch E, .] in the caller's edge order -> [batch n_dst, .]."""
+
+    @staticmethod
+    def forward(ctx, rows, ep: EdgePlan, batch: int):
+        ctx.ep, ctx.batch = ep, batch
+        return segment_sum_rows(rows, ep.num_edges, batch, batch, ep.n_dst, ep.plan.dst_ptr(), ep.perm32)
+
+    @staticmethod
+    def backward(ctx, dout):
+        from .wide import gather_rows
+
+        ep = ctx.ep
+        return gather_rows(dout.contiguous(), ep.n_dst, ep.dst32, ctx.batch, ep.num_edges), None, None
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # modules
 # ---------------------------------------------------------------------------------------------------------------------
@@ -542,6 +847,40 @@ class InteractionNetwork(nn.Module):
         h = _LinearGather.apply(aggr, n0.weight[:, dr:], n0.bias, ((None, (None, ep.ident_dst)),), p_node)
         return self.mlp_nodes.tail(self.mlp_nodes._layer(0, h))
 
+    def _forward_shared(self, x_send: torch.Tensor, x_recv: torch.Tensor, edge_index: torch.Tensor, edge_attr: torch.Tensor,
+                        batch: int, n_send: int, n_recv: int) -> torch.Tensor:
+        """``forward`` on ``batch`` copies of one graph -> [batch n_recv, .]: ``edge_index`` and ``edge_attr`` [E, .] describe one
+        copy; a node table has ``batch n`` rows (copy b at b n) or ``n`` rows (shared by the copies).  The edge-level part of the
+        first message layer, edge_attr . We^T + bias, is formed on E rows and gathered per copy: nothing of size batch E comes
+        from the edge attributes alone."""
+        ds, dr, _ = self._dims
+        ep = edge_plan(edge_index, n_send, n_recv)
+        E = ep.num_edges
+        dev = edge_attr.device
+
+        def rows_pb(t, n):  # 0: shared by the copies
+            if int(t.shape[0]) not in (n, batch * n):
+                raise RuntimeError("graph_weather_amd: a node table of a batch-shared graph has n or batch n rows")
+            return n if int(t.shape[0]) == batch * n and batch > 1 else 0
+
+        l0 = self.mlp_edges.linears[0]
+        w0 = l0.weight
+        p_recv = _Linear.apply(x_recv, w0[:, :dr], None, False)
+        p_send = _Linear.apply(x_send, w0[:, dr:dr + ds], None, False)
+        p_edge = _Linear.apply(edge_attr, w0[:, dr + ds:], l0.bias, False)  # [E, .]
+        meta = ((None, 0, (None, ep.plan.identity_ptr())), (ep.dst32, rows_pb(x_recv, n_recv), (ep.perm32, ep.plan.dst_ptr())),
+                (ep.src32, rows_pb(x_send, n_send), ep.by_src))
+        h = _LinearGatherShared.apply(None, None, None, meta, batch, E, p_edge, p_recv, p_send)
+        msg = self.mlp_edges.tail(self.mlp_edges._layer(0, h))
+        aggr = _SegmentSumShared.apply(msg, ep, batch)
+        if self.scale_factor != 1.0:
+            aggr = _RowScale.apply(aggr, torch.full((batch * n_recv,), float(self.scale_factor), dtype=torch.float32, device=dev))
+        n0 = self.mlp_nodes.linears[0]
+        p_node = _Linear.apply(x_recv, n0.weight[:, :dr], None, False)
+        h = _LinearGatherShared.apply(aggr, n0.weight[:, dr:], n0.bias, ((None, rows_pb(x_recv, n_recv), (None, ep.ident_dst)),), batch,
+                                      n_recv, p_node)
+        return self.mlp_nodes.tail(self.mlp_nodes._layer(0, h))
+
 
 class FourierEmbedding(nn.Module):
     """Fourier embedding module (modules.py)."""
@@ -581,6 +920,12 @@ class ConditionalLayerNorm(nn.Module):
         scale = _Linear.apply(cond_param, self.linear_scale.weight, self.linear_scale.bias, False)
         bias = _Linear.apply(cond_param, self.linear_bias.weight, self.linear_bias.bias, False)
         return _CondLayerNorm.apply(x, scale, bias, _act)
+
+    def _forward_grouped(self, x: torch.Tensor, cond_param: torch.Tensor, rows_per_group: int, _act: Optional[str] = None):
+        """``forward`` with one conditioning row per ``rows_per_group`` consecutive rows of x: the two Linears run on the groups."""
+        scale = _Linear.apply(cond_param, self.linear_scale.weight, self.linear_scale.bias, False)
+        bias = _Linear.apply(cond_param, self.linear_bias.weight, self.linear_bias.bias, False)
+        return _CondLayerNormGrouped.apply(x, scale, bias, rows_per_group, _act)
 
 
 class TransformerConv(nn.Module):
@@ -623,6 +968,25 @@ class TransformerConv(nn.Module):
         x_r = _Linear.apply(x, self.lin_skip.weight, self.lin_skip.bias, False)
         return _BetaGate.apply(out, x_r, self.lin_beta.weight)
 
+    def _forward_shared(self, x: torch.Tensor, edge_index: torch.Tensor, edge_attr: Optional[torch.Tensor], batch: int) -> torch.Tensor:
+        """``forward`` on x [batch n, .] over ``batch`` copies of one graph: ``edge_index`` and ``edge_attr`` [E, .] describe one
+        copy, ``lin_edge`` runs on E rows and the attention reads that one table from every copy."""
+        n = int(x.shape[0]) // batch
+        ep = edge_plan(edge_index, n, n)
+        q = _Linear.apply(x, self.lin_query.weight, self.lin_query.bias, False)
+        k = _Linear.apply(x, self.lin_key.weight, self.lin_key.bias, False)
+        v = _Linear.apply(x, self.lin_value.weight, self.lin_value.bias, False)
+        e = None
+        if self.lin_edge is not None:
+            if edge_attr is None:
+                raise RuntimeError("graph_weather_amd: this TransformerConv was built with edge_dim: edge_attr is required")
+            e = _Linear.apply(_rows_in(edge_attr, "edge_attr"), self.lin_edge.weight, None, False)
+        elif edge_attr is not None:
+            raise RuntimeError("graph_weather_amd: edge_attr given to a TransformerConv built without edge_dim")
+        out = _GraphAttentionBatched.apply(q, k, v, e, ep.plan, self.heads, not self.concat, batch)
+        x_r = _Linear.apply(x, self.lin_skip.weight, self.lin_skip.bias, False)
+        return _BetaGate.apply(out, x_r, self.lin_beta.weight)
+
 
 class CondTransformerBlock(nn.Module):
     """A single conditioned transformer block for graphs (modules.py)."""
@@ -647,6 +1011,14 @@ class CondTransformerBlock(nn.Module):
         act = _act_name(self.activation)
         if self.cond_norm is not None:
             return self.cond_norm(x, cond_param, _act=act)  # (the activation rides on the norm's kernel)
+        return _apply_act(act, x)
+
+    def _forward_shared(self, x, edge_index, edge_attr, cond_param, batch: int):
+        """``forward`` on ``batch`` copies of one graph: x [batch n, .], ``cond_param`` one row per copy."""
+        x = self.transformer_conv._forward_shared(x, edge_index, edge_attr, batch)
+        act = _act_name(self.activation)
+        if self.cond_norm is not None:
+            return self.cond_norm._forward_grouped(x, cond_param, int(x.shape[0]) // batch, _act=act)
         return _apply_act(act, x)
 
 
@@ -676,6 +1048,20 @@ class Encoder(nn.Module):
         latent_grid_nodes = _Add.apply(grid_emb, self.grid_mlp_final(grid_emb))
         return latent_grid_nodes, latent_mesh_nodes
 
+    def _forward_shared(self, input_grid_nodes: torch.Tensor, input_mesh_nodes: torch.Tensor, input_edge_attr: torch.Tensor,
+                        edge_index: torch.Tensor, batch: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``forward`` on ``batch`` copies of one graph: grid rows [batch G, .]; the mesh node features [M, .], the edge attributes
+        [E, .] and ``edge_index`` describe one copy, so ``mesh_mlp`` and ``edges_mlp`` run once -> ([batch G, .], [batch M, .])."""
+        G, M = int(input_grid_nodes.shape[0]) // batch, int(input_mesh_nodes.shape[0])
+        grid_emb = self.grid_mlp(input_grid_nodes)
+        mesh_emb = self.mesh_mlp(input_mesh_nodes)
+        edges_emb = self.edges_mlp(input_edge_attr)
+        update = self.gnn._forward_shared(grid_emb, mesh_emb, edge_index, edges_emb, batch, G, M)
+        ident = (None, edge_plan(edge_index, G, M).ident_dst)  # (the plan the interaction network just used)
+        latent_mesh_nodes = _LinearGatherShared.apply(None, None, None, ((None, 0, ident), (None, M, ident)), batch, M, mesh_emb, update)
+        latent_grid_nodes = _Add.apply(grid_emb, self.grid_mlp_final(grid_emb))
+        return latent_grid_nodes, latent_mesh_nodes
+
 
 class Decoder(nn.Module):
     """GenCast's decoder (decoder.py)."""
@@ -702,6 +1088,14 @@ class Decoder(nn.Module):
         latent_grid_nodes = _Add.apply(_rows_in(input_grid_nodes, "input_grid_nodes"),
                                        self.gnn(x=(input_mesh_nodes, input_grid_nodes), edge_index=edge_index, edge_attr=edges_emb))
         return self.grid_mlp_final(latent_grid_nodes)
+
+    def _forward_shared(self, input_mesh_nodes: torch.Tensor, input_grid_nodes: torch.Tensor, input_edge_attr: torch.Tensor,
+                        edge_index: torch.Tensor, batch: int) -> torch.Tensor:
+        """``forward`` on ``batch`` copies of one graph: node rows [batch M, .] and [batch G, .], one copy's edges."""
+        M, G = int(input_mesh_nodes.shape[0]) // batch, int(input_grid_nodes.shape[0]) // batch
+        edges_emb = self.edges_mlp(input_edge_attr)
+        update = self.gnn._forward_shared(input_mesh_nodes, input_grid_nodes, edge_index, edges_emb, batch, M, G)
+        return self.grid_mlp_final(_Add.apply(_rows_in(input_grid_nodes, "input_grid_nodes"), update))
 
 
 class Processor(nn.Module):
@@ -756,4 +1150,17 @@ class Processor(nn.Module):
         edges_emb = self.edges_mlp(input_edge_attr) if self.edges_dim is not None else None
         for cond_transformer in self.cond_transformers:
             latent_mesh_nodes = cond_transformer(x=latent_mesh_nodes, edge_index=edge_index, cond_param=noise_emb, edge_attr=edges_emb)
+        return latent_mesh_nodes
+
+    def _forward_shared(self, latent_mesh_nodes: torch.Tensor, edge_index: torch.Tensor, noise_levels: torch.Tensor,
+                        input_edge_attr: Optional[torch.Tensor], batch: int) -> torch.Tensor:
+        """``forward`` on ``batch`` copies of one graph: mesh rows [batch M, .], ``noise_levels`` [batch, 1] (one row per copy, not
+        per node), one copy's ``edge_index`` and edge attributes.  The noise embedding and every block's scale and bias run on
+        ``batch`` rows, ``edges_mlp`` and every ``lin_edge`` on E rows."""
+        if (input_edge_attr is not None) and (self.edges_dim is None):
+            raise ValueError("To use input_edge_attr initialize the processor with edges_dim.")
+        noise_emb = self.fourier_embedder(noise_levels)
+        edges_emb = self.edges_mlp(input_edge_attr) if self.edges_dim is not None else None
+        for cond_transformer in self.cond_transformers:
+            latent_mesh_nodes = cond_transformer._forward_shared(latent_mesh_nodes, edge_index, edges_emb, noise_emb, batch)
         return latent_mesh_nodes

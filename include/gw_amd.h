@@ -843,6 +843,26 @@ int gw_graph_attention_backward(int32_t n_dst, int32_t n_src, int32_t n_edges, i
                                 int32_t ld_v, const float* e, int32_t ld_e, int32_t mean, const float* out_heads, int32_t ld_out_heads,
                                 const float* dout, int32_t ld_dout, const float* lse, float* delta, float* dq, int32_t ld_dq, float* dk,
                                 int32_t ld_dk, float* dv, int32_t ld_dv, float* de, int32_t ld_de, void* stream);
+/* Batch-shared form: `batch` >= 1 disconnected copies of one graph (what the reference's utils/batching.py builds by replicating
+ * edge_index and edge_attr) share ONE plan over n_dst, n_src and n_edges.  Copy b's rows are rows b n_dst .. of q, out, out_heads,
+ * dq, dout [batch n_dst, .] and rows b n_src .. of k, v, dk, dv [batch n_src, .]; lse is [2, batch n_dst heads], delta
+ * [batch n_dst heads]; all row offsets are 64-bit.  The edge tables e and de start e_batch_stride rows further per copy:
+ * 0 = one table [n_edges, heads C] read by every copy, >= n_edges = one table per copy (anything between: GW_E_BADARG).  The work
+ * item is (copy, destination, head) with the per-item arithmetic of the calls above: on the replicated graph they give bitwise
+ * the same out, lse, dq, dk, dv.  With a shared table de [n_edges, heads C] is the sum over the copies in copy order 0, 1, ...,
+ * formed by the wave that owns the destination (plain stores, no atomics).  batch = 1 is the call above. */
+int gw_graph_attention_batched_forward(int32_t batch, int64_t e_batch_stride, int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads,
+                                       int32_t dim_head, const int32_t* dst_ptr, const int32_t* src, const int64_t* perm, const float* q,
+                                       int32_t ld_q, const float* k, int32_t ld_k, const float* v, int32_t ld_v, const float* e, int32_t ld_e,
+                                       int32_t mean, float* out, int32_t ld_out, float* out_heads, int32_t ld_out_heads, float* lse,
+                                       void* stream);
+int gw_graph_attention_batched_backward(int32_t batch, int64_t e_batch_stride, int32_t n_dst, int32_t n_src, int32_t n_edges, int32_t heads,
+                                        int32_t dim_head, const int32_t* dst_ptr, const int32_t* src, const int32_t* dst,
+                                        const int64_t* perm, const int32_t* src_pos, const int32_t* src_ptr, const float* q, int32_t ld_q,
+                                        const float* k, int32_t ld_k, const float* v, int32_t ld_v, const float* e, int32_t ld_e,
+                                        int32_t mean, const float* out_heads, int32_t ld_out_heads, const float* dout, int32_t ld_dout,
+                                        const float* lse, float* delta, float* dq, int32_t ld_dq, float* dk, int32_t ld_dk, float* dv,
+                                        int32_t ld_dv, float* de, int32_t ld_de, void* stream);
 /* ConditionalLayerNorm (modules.py): out[r] = act(scale[r] o LN(x[r]) + bias[r]) with LN = LayerNorm without affine, eps 1e-5, and
  * scale, bias one row per row of x; act = GW_ACT_*.  Backward: dx, dscale, dbias (each may be NULL; dscale and dbias share ld_dsb). */
 #define GW_ACT_NONE 0
@@ -853,6 +873,37 @@ int gw_cond_layernorm_forward(int64_t rows, int32_t width, int32_t act, const fl
 int gw_cond_layernorm_backward(int64_t rows, int32_t width, int32_t act, const float* x, int32_t ld_x, const float* scale,
                                int32_t ld_scale, const float* bias, int32_t ld_bias, const float* dout, int32_t ld_dout, float* dx,
                                int32_t ld_dx, float* dscale, float* dbias, int32_t ld_dsb, void* stream);
+/* The same with one scale and one bias row per group of rows_per_group consecutive rows (row r reads row r / rows_per_group; the
+ * last group may be shorter): the noise conditioning of a batch, one row per sample.  The forward gives bitwise what the call
+ * above gives on row-repeated scale and bias.  Backward: dx as above; dscale and dbias [groups, width] (each may be NULL) sum over
+ * the group's rows as partials per slab of 256 rows in gw_cond_layernorm_grouped_workspace_bytes (host-side query; 0 with the
+ * error set on bad arguments) of scratch, added in slab order.  At most 65535 groups and 65535 slabs per group. */
+int gw_cond_layernorm_grouped_forward(int64_t rows, int32_t width, int32_t act, int64_t rows_per_group, const float* x, int32_t ld_x,
+                                      const float* scale, int32_t ld_scale, const float* bias, int32_t ld_bias, float* out, int32_t ld_out,
+                                      void* stream);
+size_t gw_cond_layernorm_grouped_workspace_bytes(int64_t rows, int32_t width, int64_t rows_per_group);
+int gw_cond_layernorm_grouped_backward(int64_t rows, int32_t width, int32_t act, int64_t rows_per_group, const float* x, int32_t ld_x,
+                                       const float* scale, int32_t ld_scale, const float* bias, int32_t ld_bias, const float* dout,
+                                       int32_t ld_dout, void* workspace, size_t workspace_bytes, float* dx, int32_t ld_dx, float* dscale,
+                                       float* dbias, int32_t ld_dsb, void* stream);
+/* The Denoiser's preconditioning (denoiser.py, utils/noise.py; Karras et al. 2022) on rows r = b grid_rows + g of `batch` samples,
+ * sigma [batch] > 0, the coefficients formed in float32 in the reference's order of operations from sigma and d = sigma_data > 0:
+ * c_in = 1 / sqrt(sigma^2 + d^2), c_skip = d^2 / (sigma^2 + d^2), c_out = sigma d / sqrt(sigma^2 + d^2), c_noise = 1/4 log sigma.
+ * input_forward: out[r] = (c_in(sigma_b) z[r] | x[r] | stat[g]) of widths w_z, w_x, w_s - the encoder's grid input rows with the
+ * static grid features stat [grid_rows, w_s] - and c_noise [batch] (may be NULL); input_backward: dz[r] = c_in dout[r, :w_z],
+ * dx[r] = dout[r, w_z : w_z + w_x] (each may be NULL).  output_forward: out[r] = c_skip(sigma_b) z[r] + c_out(sigma_b) preds[r];
+ * output_backward: dz = c_skip dout, dpreds = c_out dout (each may be NULL).  sigma itself gets no gradient. */
+int gw_gencast_precond_input_forward(int32_t batch, int64_t grid_rows, int32_t w_z, int32_t w_x, int32_t w_s, float sigma_data,
+                                     const float* sigma, const float* z, int32_t ld_z, const float* x, int32_t ld_x, const float* stat,
+                                     int32_t ld_stat, float* out, int32_t ld_out, float* c_noise, void* stream);
+int gw_gencast_precond_input_backward(int32_t batch, int64_t grid_rows, int32_t w_z, int32_t w_x, float sigma_data, const float* sigma,
+                                      const float* dout, int32_t ld_dout, float* dz, int32_t ld_dz, float* dx, int32_t ld_dx,
+                                      void* stream);
+int gw_gencast_precond_output_forward(int32_t batch, int64_t grid_rows, int32_t width, float sigma_data, const float* sigma, const float* z,
+                                      int32_t ld_z, const float* preds, int32_t ld_preds, float* out, int32_t ld_out, void* stream);
+int gw_gencast_precond_output_backward(int32_t batch, int64_t grid_rows, int32_t width, float sigma_data, const float* sigma,
+                                       const float* dout, int32_t ld_dout, float* dz, int32_t ld_dz, float* dpreds, int32_t ld_dpreds,
+                                       void* stream);
 /* TransformerConv's beta gate: g[r] = sigmoid(w_a . out[r] + w_b . x_r[r] + w_c . (out[r] - x_r[r])), w = [w_a | w_b | w_c]
  * (lin_beta.weight, 3 width floats), y[r] = g x_r[r] + (1 - g) out[r]; gate [rows] keeps g for the backward.  Backward: d_out and
  * d_xr (each may be NULL, leading dimension ld_d) and dw [3 width], formed as partials per slab of 256 rows in
