@@ -54,6 +54,9 @@ EXPORTS = [
     "gw_graph_attention_batched_forward", "gw_graph_attention_batched_backward", "gw_cond_layernorm_grouped_forward",
     "gw_cond_layernorm_grouped_workspace_bytes", "gw_cond_layernorm_grouped_backward", "gw_gencast_precond_input_forward",
     "gw_gencast_precond_input_backward", "gw_gencast_precond_output_forward", "gw_gencast_precond_output_backward",
+    "gw_isht_lmax", "gw_isht_legendre_floats", "gw_isht_workspace_bytes", "gw_isht_forward",
+    "gw_gencast_sampler_combine", "gw_gencast_weighted_mse_workspace_bytes", "gw_gencast_weighted_mse_forward",
+    "gw_gencast_weighted_mse_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -325,6 +328,15 @@ def lib():
     L.gw_amse_backward.restype = c_int
     L.gw_amse_backward.argtypes = [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                    c_void_p, c_void_p]
+    L.gw_isht_lmax.restype = c_int32
+    L.gw_isht_lmax.argtypes = [c_int32, c_int32]
+    L.gw_isht_legendre_floats.restype = c_size_t
+    L.gw_isht_legendre_floats.argtypes = [c_int32, c_int32]
+    L.gw_isht_workspace_bytes.restype = c_size_t
+    L.gw_isht_workspace_bytes.argtypes = [c_int32, c_int32, c_int32]
+    L.gw_isht_forward.restype = c_int
+    L.gw_isht_forward.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_size_t,
+                                  c_void_p, c_void_p]
     L.gw_modulate_workspace_bytes.restype = c_size_t
     L.gw_modulate_workspace_bytes.argtypes = [c_int64, c_int64]
     L.gw_sdl_forward.restype = c_int
@@ -439,6 +451,14 @@ def lib():
     L.gw_gencast_precond_output_forward.argtypes = [c_int32, c_int64, c_int32, c_float, c_void_p] + [c_void_p, c_int32] * 3 + [c_void_p]
     L.gw_gencast_precond_output_backward.restype = c_int
     L.gw_gencast_precond_output_backward.argtypes = [c_int32, c_int64, c_int32, c_float, c_void_p] + [c_void_p, c_int32] * 3 + [c_void_p]
+    L.gw_gencast_sampler_combine.restype = c_int
+    L.gw_gencast_sampler_combine.argtypes = [c_int64, c_float, c_void_p, c_float, c_void_p, c_float, c_void_p, c_void_p, c_void_p]
+    L.gw_gencast_weighted_mse_workspace_bytes.restype = c_size_t
+    L.gw_gencast_weighted_mse_workspace_bytes.argtypes = [c_int32] * 4
+    L.gw_gencast_weighted_mse_forward.restype = c_int
+    L.gw_gencast_weighted_mse_forward.argtypes = [c_int32] * 4 + [c_float] + [c_void_p] * 6 + [c_size_t, c_void_p, c_void_p, c_void_p]
+    L.gw_gencast_weighted_mse_backward.restype = c_int
+    L.gw_gencast_weighted_mse_backward.argtypes = [c_int32] * 4 + [c_float] + [c_void_p] * 8
     L.gw_cond_layernorm_forward.restype = c_int
     L.gw_cond_layernorm_forward.argtypes = [c_int64, c_int32, c_int32] + [c_void_p, c_int32] * 4 + [c_void_p]
     L.gw_cond_layernorm_backward.restype = c_int

@@ -721,6 +721,27 @@ class AMSENormalizedFunction(torch.autograd.Function):
         return ops.amse_backward(coeff, gfac, dloss.reshape(1).contiguous().float(), ctx.shape), None, None, None
 
 
+class WeightedMSEFunction(torch.autograd.Function):
+    """GenCast's ``WeightedMSELoss.forward`` (weighted_mse_loss.py): returns (loss, NaN flag); the backward is one elementwise
+    kernel over the saved operands."""
+
+    @staticmethod
+    def forward(ctx, pred, target, sigma, area_weights, features_weights, sigma_data):
+        loss, flag = ops.weighted_mse_forward(pred, target, sigma, area_weights, features_weights, sigma_data)
+        ctx.save_for_backward(pred, target, sigma)
+        ctx.weights = (area_weights, features_weights)  # (buffers of the module, no gradient)
+        ctx.sigma_data = sigma_data
+        ctx.mark_non_differentiable(flag)
+        return loss, flag
+
+    @staticmethod
+    def backward(ctx, dloss, _dflag):
+        pred, target, sigma = ctx.saved_tensors
+        aw, fw = ctx.weights
+        dpred = ops.weighted_mse_backward(pred, target, sigma, aw, fw, dloss.reshape(1).contiguous().float(), ctx.sigma_data)
+        return dpred, None, None, None, None, None
+
+
 class StochasticDecompositionFunction(torch.autograd.Function):
     """x + (alpha * style) * eps (csrc/gw_modulate.hip).  The backward regenerates eps from the 8-byte key: only the key, style
     and alpha are saved (with ``noise`` given, that tensor instead of the key).  The gradient of x is the incoming one."""

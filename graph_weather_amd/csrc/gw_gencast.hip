@@ -1200,3 +1200,194 @@ int gw_fourier_backward(int64_t rows, int32_t num_frequencies, float base_period
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The Sampler's state updates (sampler.py) and WeightedMSELoss (weighted_mse_loss.py).
+//   combine_kernel   out = a x + b y + c z on n dense floats with host scalars; a null operand is skipped.  float4 body and a
+//                    scalar tail through one expression (a x, then fmaf for y, then fmaf for z), so an element's result does
+//                    not depend on where it sits.  out may alias x (every element is read before it is written, by its own thread).
+//   wmse_fwd_kernel  per slab of kWmseSlab elements of [B, lon, lat, var]: sum of (pred - target)^2 aw[lat] fw[var] lambda(sigma_b)
+//                    in fp64, lambda(s) = (s^2 + d^2) / (s d)^2 formed in float32 as the reference forms it, and a flag that a
+//                    squared residual was NaN; wmse_final_kernel adds the slabs' sums as a fixed-shape tree and ORs the flags.
+//   wmse_bwd_kernel  dpred = dloss * 2 (pred - target) aw fw lambda / n.
+// No atomics: equal inputs give bitwise equal results.
+namespace {
+
+constexpr int kWmseSlab = 4096;  // elements per workgroup of wmse_fwd_kernel (16 per thread)
+
+__device__ inline float combine1(bool hx, bool hy, bool hz, float a, float b, float c, float x, float y, float z) {
+  float r = hx ? __fmul_rn(a, x) : 0.f;
+  if (hy) r = hx ? fmaf(b, y, r) : __fmul_rn(b, y);
+  if (hz) r = (hx || hy) ? fmaf(c, z, r) : __fmul_rn(c, z);
+  return r;
+}
+
+__global__ __launch_bounds__(256) void combine_kernel(long long n, long long n4, float a, float b, float c, const float* x, const float* y,
+                                                      const float* z, float* out) {
+  const bool hx = x != nullptr, hy = y != nullptr, hz = z != nullptr;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 vx = hx ? ((const float4*)x)[i] : zero, vy = hy ? ((const float4*)y)[i] : zero, vz = hz ? ((const float4*)z)[i] : zero;
+    float4 r;
+    r.x = combine1(hx, hy, hz, a, b, c, vx.x, vy.x, vz.x);
+    r.y = combine1(hx, hy, hz, a, b, c, vx.y, vy.y, vz.y);
+    r.z = combine1(hx, hy, hz, a, b, c, vx.z, vy.z, vz.z);
+    r.w = combine1(hx, hy, hz, a, b, c, vx.w, vy.w, vz.w);
+    ((float4*)out)[i] = r;
+  }
+  for (long long i = 4 * n4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+    out[i] = combine1(hx, hy, hz, a, b, c, hx ? x[i] : 0.f, hy ? y[i] : 0.f, hz ? z[i] : 0.f);
+}
+
+__device__ inline float wmse_lambda(float s, float d) {
+  const float sd = __fmul_rn(s, d);
+  return __fdiv_rn(__fadd_rn(__fmul_rn(s, s), __fmul_rn(d, d)), __fmul_rn(sd, sd));
+}
+
+// weight of element e of [B, lon, lat, var]: aw[lat] fw[var] (each optional), and its sample
+__device__ inline float wmse_weight(long long e, int nlat, int nvar, long long per_sample, const float* aw, const float* fw, int* sample) {
+  const long long row = e / nvar;
+  float w = 1.f;
+  if (aw) w = aw[(int)(row % nlat)];
+  if (fw) w = __fmul_rn(w, fw[(int)(e - row * nvar)]);
+  *sample = (int)(e / per_sample);
+  return w;
+}
+
+__global__ __launch_bounds__(256) void wmse_fwd_kernel(long long n, int nlat, int nvar, long long per_sample, float d,
+                                                       const float* __restrict__ pred, const float* __restrict__ target,
+                                                       const float* __restrict__ sigma, const float* __restrict__ aw,
+                                                       const float* __restrict__ fw, double* __restrict__ part, int* __restrict__ flags) {
+  __shared__ double red[256];
+  __shared__ int bad[256];
+  const long long e0 = (long long)blockIdx.x * kWmseSlab;
+  double s = 0.0;
+  int nan = 0;
+  for (int i = 0; i < kWmseSlab / 256; ++i) {
+    const long long e = e0 + i * 256 + threadIdx.x;
+    if (e >= n) break;
+    const float r = __fsub_rn(pred[e], target[e]), sq = __fmul_rn(r, r);
+    nan |= (sq != sq);
+    int b;
+    const float w = wmse_weight(e, nlat, nvar, per_sample, aw, fw, &b);
+    s += (double)__fmul_rn(sq, w) * (double)wmse_lambda(sigma[b], d);
+  }
+  red[threadIdx.x] = s;
+  bad[threadIdx.x] = nan;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) {
+      red[threadIdx.x] += red[threadIdx.x + w];
+      bad[threadIdx.x] |= bad[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    part[blockIdx.x] = red[0];
+    flags[blockIdx.x] = bad[0];
+  }
+}
+
+// one workgroup
+__global__ __launch_bounds__(256) void wmse_final_kernel(long long slabs, long long n, const double* __restrict__ part,
+                                                         const int* __restrict__ flags, float* __restrict__ loss, int* __restrict__ nan_flag) {
+  __shared__ double red[256];
+  __shared__ int bad[256];
+  double s = 0.0;
+  int nan = 0;
+  for (long long i = threadIdx.x; i < slabs; i += 256) {
+    s += part[i];
+    nan |= flags[i];
+  }
+  red[threadIdx.x] = s;
+  bad[threadIdx.x] = nan;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (threadIdx.x < w) {
+      red[threadIdx.x] += red[threadIdx.x + w];
+      bad[threadIdx.x] |= bad[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    *loss = (float)(red[0] / (double)n);
+    *nan_flag = bad[0];
+  }
+}
+
+__global__ __launch_bounds__(256) void wmse_bwd_kernel(long long n, int nlat, int nvar, long long per_sample, float d,
+                                                       const float* __restrict__ pred, const float* __restrict__ target,
+                                                       const float* __restrict__ sigma, const float* __restrict__ aw,
+                                                       const float* __restrict__ fw, const float* __restrict__ dloss,
+                                                       float* __restrict__ dpred) {
+  const float g = (float)(2.0 * (double)*dloss / (double)n);
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += stride) {
+    int b;
+    const float w = wmse_weight(e, nlat, nvar, per_sample, aw, fw, &b);
+    dpred[e] = __fmul_rn(__fmul_rn(g, __fsub_rn(pred[e], target[e])), __fmul_rn(w, wmse_lambda(sigma[b], d)));
+  }
+}
+
+bool wmse_ok(int32_t batch, int32_t nlon, int32_t nlat, int32_t nvar, float sigma_data) {
+  return batch >= 1 && nlon >= 1 && nlat >= 1 && nvar >= 1 && sigma_data > 0.f;
+}
+
+long long wmse_count(int32_t batch, int32_t nlon, int32_t nlat, int32_t nvar) { return (long long)batch * nlon * nlat * nvar; }
+
+size_t wmse_bytes(long long n) { return (size_t)((n + kWmseSlab - 1) / kWmseSlab) * (sizeof(double) + sizeof(int)); }
+
+}  // namespace
+
+extern "C" {
+
+int gw_gencast_sampler_combine(int64_t n, float a, const float* x, float b, const float* y, float c, const float* z, float* out,
+                               void* stream) {
+  if (n < 0 || !out || (!x && !y && !z)) return failf(GW_E_BADARG, "gw_gencast_sampler_combine: bad arguments");
+  if (n == 0) return GW_OK;
+  const uintptr_t bits = (uintptr_t)out | (uintptr_t)x | (uintptr_t)y | (uintptr_t)z;  // (a null operand adds no bits)
+  const long long n4 = (bits & 15) ? 0 : n / 4;
+  hipLaunchKernelGGL(combine_kernel, dim3(grid_for(n4 ? n4 : n)), dim3(256), 0, (hipStream_t)stream, (long long)n, n4, a, b, c, x, y, z,
+                     out);
+  return check_launch("combine_kernel launch");
+}
+
+size_t gw_gencast_weighted_mse_workspace_bytes(int32_t batch, int32_t nlon, int32_t nlat, int32_t nvar) {
+  if (!wmse_ok(batch, nlon, nlat, nvar, 1.f)) {
+    failf(GW_E_BADARG, "gw_gencast_weighted_mse_workspace_bytes: bad arguments");
+    return 0;
+  }
+  return wmse_bytes(wmse_count(batch, nlon, nlat, nvar));
+}
+
+int gw_gencast_weighted_mse_forward(int32_t batch, int32_t nlon, int32_t nlat, int32_t nvar, float sigma_data, const float* pred,
+                                    const float* target, const float* sigma, const float* area_weights, const float* features_weights,
+                                    void* workspace, size_t workspace_bytes, float* loss, int32_t* nan_flag, void* stream) {
+  if (!wmse_ok(batch, nlon, nlat, nvar, sigma_data) || !pred || !target || !sigma || !loss || !nan_flag)
+    return failf(GW_E_BADARG, "gw_gencast_weighted_mse_forward: bad arguments");
+  const long long n = wmse_count(batch, nlon, nlat, nvar), slabs = (n + kWmseSlab - 1) / kWmseSlab;
+  if (slabs > INT32_MAX) return failf(GW_E_UNSUPPORTED, "gw_gencast_weighted_mse_forward: shape too large");
+  if (!workspace || workspace_bytes < wmse_bytes(n)) return failf(GW_E_BADARG, "gw_gencast_weighted_mse_forward: bad arguments (workspace)");
+  double* part = (double*)workspace;
+  int* flags = (int*)(part + slabs);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(wmse_fwd_kernel, dim3((unsigned)slabs), dim3(256), 0, st, n, (int)nlat, (int)nvar, n / batch, sigma_data, pred, target,
+                     sigma, area_weights, features_weights, part, flags);
+  if (int rc = check_launch("wmse_fwd_kernel launch")) return rc;
+  hipLaunchKernelGGL(wmse_final_kernel, dim3(1), dim3(256), 0, st, slabs, n, (const double*)part, (const int*)flags, loss, (int*)nan_flag);
+  return check_launch("wmse_final_kernel launch");
+}
+
+int gw_gencast_weighted_mse_backward(int32_t batch, int32_t nlon, int32_t nlat, int32_t nvar, float sigma_data, const float* pred,
+                                     const float* target, const float* sigma, const float* area_weights, const float* features_weights,
+                                     const float* dloss, float* dpred, void* stream) {
+  if (!wmse_ok(batch, nlon, nlat, nvar, sigma_data) || !pred || !target || !sigma || !dloss || !dpred)
+    return failf(GW_E_BADARG, "gw_gencast_weighted_mse_backward: bad arguments");
+  const long long n = wmse_count(batch, nlon, nlat, nvar);
+  hipLaunchKernelGGL(wmse_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, n, (int)nlat, (int)nvar, n / batch, sigma_data,
+                     pred, target, sigma, area_weights, features_weights, dloss, dpred);
+  return check_launch("wmse_bwd_kernel launch");
+}
+
+}  // extern "C"

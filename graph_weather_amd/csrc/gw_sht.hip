@@ -471,3 +471,168 @@ int gw_amse_backward(int32_t fields, int32_t nlat, int32_t nlon, const float* co
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The inverse transform: torch_harmonics.InverseRealSHT(nlat, nlon, lmax, mmax = lmax + 1, grid="equiangular"), which GenCast's
+// generate_isotropic_noise (utils/noise.py) applies to white coefficients.  Two products with the structure of the adjoint pair
+// above, on unweighted Legendre functions and the irfft matrix (no quadrature weights, no loss terms):
+//   isht_lat_kernel   per order m: G_c[m, k, q] = sum_{l >= m} c_c[q, l, m] * P[m, l, k], c = re / im, straight from the
+//                     interleaved complex64 coefficients [fields, lmax, mmax].  The K range starts at l = m.  The imaginary
+//                     part of m = 0 is read as zero (irfft ignores it); the order m = lmax = nlon / 2 has no degree l < lmax
+//                     at all, so it is never visited and its imaginary part is ignored too.
+//   isht_lon_kernel   out[b, j, k, ch] = scale * sum_{c, m < lmax} D[c, m, j] * G_c[m, k, q], q = b * C + ch, folded about
+//                     j = nlon / 2 as lon_bwd_kernel folds.  The rows of G are (k, q) with q fastest, so the 16 lanes of an
+//                     accumulator column write consecutive channels of the final [B, lon, lat, C] layout: no permute pass.
+// One fixed summation order per output element, independent of the number of fields; no atomics; no host synchronisation.
+namespace {
+
+// lmax of the two grids generate_isotropic_noise accepts, 0 for any other
+int isht_lmax(int nlat, int nlon) {
+  if (nlat < 2 || nlon < 2) return 0;
+  if (nlon == 2 * nlat) return nlat;
+  if (nlon == 2 * (nlat - 1)) return nlat - 1;
+  return 0;
+}
+
+bool make_isht_geom(int32_t fields, int32_t channels, int32_t nlat, int32_t nlon, Geom* g) {
+  const int L = isht_lmax(nlat, nlon);
+  if (fields < 1 || channels < 1 || fields % channels || L < 1) return false;
+  g->N = fields;
+  g->C = channels;
+  g->H = nlat;
+  g->W = nlon;
+  g->L = L;
+  g->M = L + 1;
+  g->Mp = (g->M + kTile - 1) / kTile * kTile;
+  g->Kf = nlon / 2 + 1;
+  return true;
+}
+
+size_t isht_bytes(const Geom& g) { return align256((size_t)2 * g.L * g.N * g.H * sizeof(float)); }
+
+// grid (lmax orders, latitude tiles, tiles of 32 fields), block 256.  Tile rows are latitudes, tile columns (c, field): columns
+// [0, 32) the real parts of 32 fields, [32, 64) their imaginary parts.  G[((c * L + m) * H + k) * N + q].
+__global__ __launch_bounds__(256) void isht_lat_kernel(Geom g, const float* __restrict__ coef, const float* __restrict__ leg,
+                                                       float* __restrict__ G) {
+  __shared__ float As[kTile * kLd];
+  __shared__ float Bs[kTile * kLd];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x, h0 = blockIdx.y * kTile, n0 = blockIdx.z * 32;
+  const float* Pm = leg + tri_off(m, g.L, g.H);
+  sh_f32x4 acc[2][2];
+  zero_acc(acc);
+  auto la = [&](int r, int k) -> float {
+    const int h = h0 + r;
+    return (h < g.H && m + k < g.L) ? Pm[(int64_t)k * g.H + h] : 0.f;
+  };
+  auto lb = [&](int col, int k) -> float {
+    const int c = col >> 5, n = n0 + (col & 31), l = m + k;
+    if (n >= g.N || l >= g.L || (c && m == 0)) return 0.f;
+    return coef[(((int64_t)n * g.L + l) * g.M + m) * 2 + c];
+  };
+  tile_product<2, 2, false, true>(acc, 0, g.L - m, la, lb, As, Bs);
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+  const int c = wn >> 5;  // a wave's 32 columns are all real or all imaginary
+  float* Gm = G + ((int64_t)c * g.L + m) * g.H * g.N;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int n = n0 + j * 16 + (lane & 15);
+    if (n >= g.N) continue;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int h = h0 + wm + i * 16 + 4 * (lane >> 4) + r;
+        if (h < g.H) Gm[(int64_t)h * g.N + n] = acc[i][j][r];
+      }
+  }
+}
+
+// grid (tiles of the (k, q) rows of G over H N, tiles of the folded longitudes), block 256.  Tile rows are longitudes, tile
+// columns the rows of G.
+__global__ __launch_bounds__(256) void isht_lon_kernel(Geom g, const float* __restrict__ G, const float* __restrict__ syn, float scale,
+                                                       float* __restrict__ out) {
+  __shared__ float As[kTile * kLd];
+  __shared__ float Bs[kTile * kLd];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t R = (int64_t)g.H * g.N;
+  const int64_t q0 = (int64_t)blockIdx.x * kTile;
+  const int j0 = blockIdx.y * kTile;
+  sh_f32x4 even[2][2], odd[2][2];
+  zero_acc(even);
+  zero_acc(odd);
+  auto half = [&](int c, sh_f32x4(&acc)[2][2]) {
+    auto la = [&](int r, int k) -> float {
+      const int j = j0 + r;
+      return (j < g.Kf && k < g.L) ? syn[((int64_t)c * g.Mp + k) * g.W + j] : 0.f;
+    };
+    auto lb = [&](int col, int k) -> float {
+      const int64_t q = q0 + col;
+      return (q < R && k < g.L) ? G[((int64_t)c * g.L + k) * R + q] : 0.f;
+    };
+    tile_product<2, 2, false, false>(acc, 0, g.L, la, lb, As, Bs);
+  };
+  half(0, even);
+  half(1, odd);
+  const int wm = (wave & 1) * 32, wn = (wave >> 1) * 32;
+#pragma unroll
+  for (int jb = 0; jb < 2; ++jb) {
+    const int64_t row = q0 + wn + jb * 16 + (lane & 15);
+    if (row >= R) continue;
+    const int k = (int)(row / g.N), q = (int)(row % g.N);
+    const int b = q / g.C, ch = q % g.C;
+    float* o = out + ((int64_t)b * g.W * g.H + k) * g.C + ch;  // + j * H * C
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int j = j0 + wm + i * 16 + 4 * (lane >> 4) + r;
+        if (j >= g.Kf) continue;
+        const float e = even[i][jb][r], d = odd[i][jb][r];
+        o[(int64_t)j * g.H * g.C] = scale * (e + d);
+        if (j > 0 && 2 * j != g.W) o[(int64_t)(g.W - j) * g.H * g.C] = scale * (e - d);
+      }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t gw_isht_lmax(int32_t nlat, int32_t nlon) { return isht_lmax(nlat, nlon); }
+
+size_t gw_isht_legendre_floats(int32_t nlat, int32_t nlon) {
+  const int L = isht_lmax(nlat, nlon);
+  return L ? (size_t)tri_off(L + 1, L, nlat) : 0;
+}
+
+size_t gw_isht_workspace_bytes(int32_t fields, int32_t nlat, int32_t nlon) {
+  Geom g;
+  if (!make_isht_geom(fields, 1, nlat, nlon, &g)) {
+    set_error(GW_E_BADARG, "gw_isht_workspace_bytes: fields >= 1 and nlon = 2 nlat or 2 (nlat - 1) are required");
+    return 0;
+  }
+  return isht_bytes(g);
+}
+
+int gw_isht_forward(int32_t fields, int32_t channels, int32_t nlat, int32_t nlon, const float* coeffs, const float* synthesis,
+                    const float* legendre, float scale, void* workspace, size_t workspace_bytes, float* out, void* stream) {
+  Geom g;
+  if (!make_isht_geom(fields, channels, nlat, nlon, &g))
+    return fail("gw_isht_forward: fields a positive multiple of channels and nlon = 2 nlat or 2 (nlat - 1) are required");
+  if (!coeffs || !synthesis || !legendre || !out) return fail("gw_isht_forward: null operand");
+  const int64_t R = (int64_t)g.N * g.H;
+  if (R > INT32_MAX / 4 || R * g.W > ((int64_t)1 << 40) || (g.N + 31) / 32 > 65535)
+    return set_error(GW_E_UNSUPPORTED, "gw_isht_forward: shape too large");
+  if (!workspace || workspace_bytes < isht_bytes(g)) return fail("gw_isht_forward: workspace smaller than gw_isht_workspace_bytes");
+  float* G = (float*)workspace;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(isht_lat_kernel, dim3(g.L, (g.H + kTile - 1) / kTile, (g.N + 31) / 32), dim3(256), 0, s, g, coeffs, legendre, G);
+  int rc = check_launch("isht_lat_kernel launch");
+  if (rc != GW_OK) return rc;
+  hipLaunchKernelGGL(isht_lon_kernel, dim3((unsigned)((R + kTile - 1) / kTile), (unsigned)((g.Kf + kTile - 1) / kTile)), dim3(256), 0, s, g,
+                     (const float*)G, synthesis, scale, out);
+  return check_launch("isht_lon_kernel launch");
+}
+
+}  // extern "C"

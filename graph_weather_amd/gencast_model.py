@@ -11,6 +11,9 @@ batch-shared form of the layers (``gencast.Encoder._forward_shared`` and its sib
 -> Decoder -> output combine - and gives the reference's result.  ``batch`` and ``hetero_batch`` stay available, and
 ``_forward_replicated`` runs the reference's route through them and the layers' public ``forward``s for comparison.
 
+``generate_isotropic_noise`` draws on the device (inverse spherical-harmonic transform of csrc/gw_sht.hip); the ``Sampler`` and
+``WeightedMSELoss`` live in ``gencast_sampler``.
+
 Not reproduced: the reference's ``assert not torch.isnan(...)`` after every stage - each one is a host synchronisation.  The
 "strictly positive" check reads the device too; it is kept (with the reference's ``.any()``) but skipped while the current stream
 is capturing, so the eval forward can be captured in a ``torch.cuda.graph``.  fp32 only; ``sparse=True`` is not provided.
@@ -63,9 +66,49 @@ def hetero_batch(senders, receivers, edge_index, edge_attr=None, batch_size=1):
 # ---------------------------------------------------------------------------------------------------------------------
 # utils/noise.py
 # ---------------------------------------------------------------------------------------------------------------------
-def generate_isotropic_noise(num_lon: int, num_lat: int, num_samples=1, isotropic=True):
-    raise NotImplementedError("graph_weather_amd: generate_isotropic_noise needs torch_harmonics (the inverse spherical harmonic "
-                              "transform), which this package does not provide")
+def generate_isotropic_noise(num_lon: int, num_lat: int, num_samples=1, isotropic=True, *, device=None, generator=None, batch=None,
+                             coeffs=None):
+    """Noise on the grid, on the device: float32 [lon, lat, num_samples], or [batch, lon, lat, num_samples] with ``batch``.
+
+    ``isotropic=True`` is white noise on the sphere: complex64 standard normal coefficients [fields, lmax, lmax + 1] divided by
+    ``sqrt(num_lat**2 // 2)``, the inverse spherical-harmonic transform (``ops.isht_forward``, csrc/gw_sht.hip: what the reference
+    gets from ``torch_harmonics.InverseRealSHT``) and a factor ``sqrt(2 pi)``; the grid must be 2N x N or 2N x (N + 1).
+    ``coeffs`` supplies the unscaled complex draws instead of ``torch.randn(..., generator=generator)``.  ``isotropic=False`` is
+    ``torch.randn`` of the output shape.
+
+    The reference returns a numpy array from the host; this package has no CPU path, so without ``device`` the function raises."""
+    if device is None:
+        raise NotImplementedError("graph_weather_amd: generate_isotropic_noise on the host needs torch_harmonics (the inverse spherical "
+                                  "harmonic transform), which this package does not provide; pass device= to draw on a HIP device")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("graph_weather_amd: generate_isotropic_noise draws on a HIP device (no CPU path exists), got %s" % device)
+    if isotropic:
+        if 2 * num_lat == num_lon:
+            extend = False
+        elif 2 * (num_lat - 1) == num_lon:
+            extend = True
+        else:
+            raise ValueError(
+                "Isotropic noise requires grid's shape to be 2N x N or 2N x (N+1): "
+                f"got {num_lon} x {num_lat}. If the shape is correct, please specify"
+                "isotropic=False in the constructor.",
+            )
+    lead = () if batch is None else (int(batch),)
+    if not isotropic:
+        return torch.randn(*lead, num_lon, num_lat, num_samples, dtype=torch.float32, device=device, generator=generator)
+    from . import ops
+
+    fields = (1 if batch is None else int(batch)) * num_samples
+    lmax = num_lat - 1 if extend else num_lat
+    mmax = lmax + 1
+    if coeffs is None:
+        coeffs = torch.randn(fields, lmax, mmax, dtype=torch.complex64, device=device, generator=generator)
+    elif tuple(coeffs.shape) != (fields, lmax, mmax):
+        raise ValueError(f"coeffs must be complex64 of shape {(fields, lmax, mmax)}, got {tuple(coeffs.shape)}")
+    coeffs = coeffs / np.sqrt((num_lat**2) // 2)
+    noise = ops.isht_forward(coeffs.contiguous(), num_lat, num_lon, num_samples, float(np.sqrt(2 * np.pi)))
+    return noise if batch is not None else noise[0]
 
 
 def sample_noise_level(sigma_min=0.02, sigma_max=88, rho=7):
@@ -188,6 +231,11 @@ class Denoiser(torch.nn.Module, PyTorchModelHubMixin):
         paired row by row with the builder's latitude-major grid nodes, as the reference pairs them."""
         self._check_shapes(corrupted_targets, prev_inputs, noise_levels)
         self._check_noise(noise_levels)
+        return self._forward_impl(corrupted_targets, prev_inputs, noise_levels)
+
+    def _forward_impl(self, corrupted_targets: torch.Tensor, prev_inputs: torch.Tensor, noise_levels: torch.Tensor) -> torch.Tensor:
+        """``forward`` without its checks (the positivity check reads the device): for callers such as ``Sampler`` whose shapes
+        are checked once and whose noise levels are known positive on the host."""
         B, sd = int(prev_inputs.shape[0]), float(self.precs.sigma_data)
         z = corrupted_targets.reshape(-1, self.output_features_dim)
         x = prev_inputs.reshape(-1, 2 * self.input_features_dim)

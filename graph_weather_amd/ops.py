@@ -579,6 +579,114 @@ def amse_backward(coeff: torch.Tensor, gfac: torch.Tensor, dloss: torch.Tensor, 
     return dpred
 
 
+_ISHT_TABLES: dict = {}
+
+
+def isht_tables(nlat: int, nlon: int, device: torch.device):
+    """Device tables of the inverse spherical-harmonic transform (``sht_tables.isht_device_tables``), built once per
+    ``(nlat, nlon, device)`` on the host in float64 and uploaded as float32."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (int(nlat), int(nlon), device)
+    hit = _ISHT_TABLES.get(key)
+    if hit is None:
+        from . import sht_tables
+
+        need = sht_tables.isht_table_bytes(nlat, nlon)
+        free, _ = torch.cuda.mem_get_info(device)
+        if need > free:
+            raise RuntimeError("graph_weather_amd: the inverse spherical-harmonic tables of a %d x %d grid need %d bytes of device "
+                               "memory, %d are free" % (nlat, nlon, need, free))
+        syn, leg = sht_tables.isht_device_tables(nlat, nlon)
+        hit = (torch.from_numpy(syn).to(device), torch.from_numpy(leg).to(device))
+        _ISHT_TABLES[key] = hit
+    return hit
+
+
+def isht_forward(coeffs: torch.Tensor, nlat: int, nlon: int, channels: int, scale: float = 1.0) -> torch.Tensor:
+    """``scale * torch_harmonics.InverseRealSHT(nlat, nlon, lmax, lmax + 1, grid="equiangular")(coeffs)`` for complex64
+    ``coeffs`` [fields, lmax, lmax + 1], written as [fields / channels, nlon, nlat, channels] (field ``b * channels + ch``)."""
+    _require(coeffs, "coeffs", torch.complex64)
+    L = _lib.lib()
+    lmax = L.gw_isht_lmax(int(nlat), int(nlon))
+    if not lmax or coeffs.dim() != 3 or tuple(coeffs.shape[1:]) != (lmax, lmax + 1) or coeffs.shape[0] < 1 or coeffs.shape[0] % channels:
+        raise RuntimeError("graph_weather_amd: the inverse transform of a %d x %d grid expects coefficients [fields, lmax, lmax + 1] with "
+                           "fields a multiple of %d, got %s" % (nlon, nlat, channels, tuple(coeffs.shape)))
+    n = int(coeffs.shape[0])
+    syn, leg = isht_tables(nlat, nlon, coeffs.device)
+    ws = torch.empty(L.gw_isht_workspace_bytes(n, nlat, nlon), dtype=torch.uint8, device=coeffs.device)
+    out = torch.empty((n // channels, nlon, nlat, channels), dtype=torch.float32, device=coeffs.device)
+    with on_device_of(coeffs):
+        _lib.check(L.gw_isht_forward(n, int(channels), int(nlat), int(nlon), torch.view_as_real(coeffs).data_ptr(), syn.data_ptr(),
+                                     leg.data_ptr(), float(scale), ws.data_ptr(), ws.numel(), out.data_ptr(), _stream(coeffs)),
+                   "gw_isht_forward")
+    return out
+
+
+def sampler_combine(out: torch.Tensor, a: float, x: Optional[torch.Tensor], b: float = 0.0, y: Optional[torch.Tensor] = None,
+                    c: float = 0.0, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out = a x + b y + c z`` with host scalars (csrc/gw_gencast.hip); an operand that is None is skipped, ``out`` may be ``x``."""
+    _require(out, "out")
+    for name, t in (("x", x), ("y", y), ("z", z)):
+        if t is not None:
+            _require(t, name)
+            if t.numel() != out.numel() or t.device != out.device:
+                raise RuntimeError("graph_weather_amd: sampler_combine operands must have out's size and device")
+    if x is None and y is None and z is None:
+        raise RuntimeError("graph_weather_amd: sampler_combine needs at least one operand")
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with on_device_of(out):
+        _lib.check(_lib.lib().gw_gencast_sampler_combine(out.numel(), float(a), ptr(x), float(b), ptr(y), float(c), ptr(z), out.data_ptr(),
+                                                         _stream(out)), "gw_gencast_sampler_combine")
+    return out
+
+
+def _wmse_operands(pred, target, sigma, area_weights, features_weights):
+    _require(pred, "pred")
+    _require(target, "target")
+    _require(sigma, "noise_level")
+    b, nlon, nlat, nvar = (int(v) for v in pred.shape)
+    for name, w, size in (("area_weights", area_weights, nlat), ("features_weights", features_weights, nvar)):
+        if w is not None:
+            _require(w, name)
+            if w.numel() != size:
+                raise RuntimeError("graph_weather_amd: %s must hold %d values, got %d" % (name, size, w.numel()))
+    return b, nlon, nlat, nvar
+
+
+def weighted_mse_forward(pred: torch.Tensor, target: torch.Tensor, sigma: torch.Tensor, area_weights: Optional[torch.Tensor],
+                         features_weights: Optional[torch.Tensor], sigma_data: float = 1.0):
+    """``WeightedMSELoss.forward`` (weighted_mse_loss.py) on [B, lon, lat, var]: (scalar loss, int32 flag [1] that a squared residual
+    was NaN), both on the device."""
+    b, nlon, nlat, nvar = _wmse_operands(pred, target, sigma, area_weights, features_weights)
+    L = _lib.lib()
+    ws = torch.empty(L.gw_gencast_weighted_mse_workspace_bytes(b, nlon, nlat, nvar), dtype=torch.uint8, device=pred.device)
+    loss = torch.empty((), dtype=torch.float32, device=pred.device)
+    flag = torch.empty(1, dtype=torch.int32, device=pred.device)
+    with on_device_of(pred):
+        _lib.check(L.gw_gencast_weighted_mse_forward(b, nlon, nlat, nvar, float(sigma_data), pred.data_ptr(), target.data_ptr(),
+                                                     sigma.data_ptr(), None if area_weights is None else area_weights.data_ptr(),
+                                                     None if features_weights is None else features_weights.data_ptr(), ws.data_ptr(),
+                                                     ws.numel(), loss.data_ptr(), flag.data_ptr(), _stream(pred)),
+                   "gw_gencast_weighted_mse_forward")
+    return loss, flag
+
+
+def weighted_mse_backward(pred: torch.Tensor, target: torch.Tensor, sigma: torch.Tensor, area_weights: Optional[torch.Tensor],
+                          features_weights: Optional[torch.Tensor], dloss: torch.Tensor, sigma_data: float = 1.0) -> torch.Tensor:
+    b, nlon, nlat, nvar = _wmse_operands(pred, target, sigma, area_weights, features_weights)
+    _require(dloss, "dloss")
+    dpred = torch.empty_like(pred)
+    with on_device_of(pred):
+        _lib.check(_lib.lib().gw_gencast_weighted_mse_backward(b, nlon, nlat, nvar, float(sigma_data), pred.data_ptr(), target.data_ptr(),
+                                                               sigma.data_ptr(), None if area_weights is None else area_weights.data_ptr(),
+                                                               None if features_weights is None else features_weights.data_ptr(),
+                                                               dloss.data_ptr(), dpred.data_ptr(), _stream(pred)),
+                   "gw_gencast_weighted_mse_backward")
+    return dpred
+
+
 def _modulate_rows(x: torch.Tensor) -> Tuple[int, int, int]:
     """(rows, channels, spatial) of a dense [B, C, *spatial] tensor as csrc/gw_modulate.hip reads it."""
     rows, channels = int(x.shape[0]) * int(x.shape[1]), int(x.shape[1])

@@ -129,3 +129,64 @@ def device_tables(nlat: int, nlon: int):
     dft[:mmax] = d[:, :mmax].T
     dft[mp:mp + mmax] = d[:, mmax:].T
     return dft, packed_latitude_table(nlat, nlon)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The inverse transform behind GenCast's generate_isotropic_noise: torch_harmonics.InverseRealSHT(nlat, nlon, lmax, mmax = lmax + 1,
+# grid="equiangular").  Unweighted Legendre functions for l < lmax and the irfft(norm="forward") matrix.
+# ---------------------------------------------------------------------------------------------------------------------
+def isht_lmax(nlat: int, nlon: int) -> int:
+    """lmax of the two grids the reference's ``generate_isotropic_noise`` accepts; 0 for any other shape."""
+    if nlat < 2 or nlon < 2:
+        return 0
+    if nlon == 2 * nlat:
+        return nlat
+    if nlon == 2 * (nlat - 1):
+        return nlat - 1
+    return 0
+
+
+def isht_packed_legendre_table(nlat: int, nlon: int, dtype=np.float32) -> np.ndarray:
+    """``Pbar_l^m(cos theta_k)`` for ``m <= l < lmax``, packed triangularly order by order (``triangular_offset(m, lmax, nlat)``).
+    The last order ``m = lmax`` of ``mmax = lmax + 1`` has no degree below lmax and takes no room."""
+    lmax = isht_lmax(nlat, nlon)
+    if not lmax:
+        raise ValueError("the inverse transform needs nlon = 2 nlat or nlon = 2 (nlat - 1), got %d x %d" % (nlon, nlat))
+    out = np.empty(triangular_offset(lmax + 1, lmax, nlat), dtype=dtype)
+    # legendre_orders yields l < nlat for m < min(nlat, nlon // 2 + 1): every order below lmax, with at least lmax - m rows
+    for m, pm in legendre_orders(nlat, nlon):
+        if m >= lmax:
+            break
+        o = triangular_offset(m, lmax, nlat)
+        out[o:o + (lmax - m) * nlat] = pm[:lmax - m].reshape(-1)
+    return out
+
+
+def synthesis_matrix(nlon: int, mmax: int) -> np.ndarray:
+    """``S`` [2 * mmax, nlon]: ``irfft(G, n=nlon, norm="forward") = G.real @ S[:mmax] + G.imag @ S[mmax:]`` for ``G`` of
+    ``mmax <= nlon // 2 + 1`` orders - ``w_m cos(2 pi m j / nlon)`` and ``-w_m sin(...)``, ``w_0 = w_{nlon/2} = 1``, else 2.  The
+    sine rows of m = 0 and m = nlon / 2 are exactly zero: irfft ignores those imaginary parts."""
+    m = np.arange(mmax)
+    # the phase is reduced in integers first, as in dft_matrix
+    ang = 2.0 * np.pi * np.mod(m[:, None] * np.arange(nlon)[None, :], nlon).astype(np.float64) / nlon
+    w = np.where((m == 0) | (2 * m == nlon), 1.0, 2.0)[:, None]
+    sin = -w * np.sin(ang)
+    sin[(m == 0) | (2 * m == nlon)] = 0.0
+    return np.concatenate([w * np.cos(ang), sin], axis=0)
+
+
+def isht_table_bytes(nlat: int, nlon: int) -> int:
+    lmax = isht_lmax(nlat, nlon)
+    rows = 2 * ((lmax + 1 + TILE - 1) // TILE) * TILE
+    return 4 * (rows * nlon + triangular_offset(lmax + 1, lmax, nlat))
+
+
+def isht_device_tables(nlat: int, nlon: int):
+    """(synthesis [2 * Mp, nlon], legendre [packed]) as float32 numpy arrays in the layout ``gw_isht_forward`` reads."""
+    mmax = isht_lmax(nlat, nlon) + 1
+    mp = ((mmax + TILE - 1) // TILE) * TILE
+    s = synthesis_matrix(nlon, mmax)
+    syn = np.zeros((2 * mp, nlon), dtype=np.float32)
+    syn[:mmax] = s[:mmax]
+    syn[mp:mp + mmax] = s[mmax:]
+    return syn, isht_packed_legendre_table(nlat, nlon)

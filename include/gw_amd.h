@@ -635,6 +635,24 @@ int gw_amse_forward(int32_t fields, int32_t channels, int32_t nlat, int32_t nlon
 int gw_amse_backward(int32_t fields, int32_t nlat, int32_t nlon, const float* coeff, const float* gfac, const float* dloss,
                      const float* dft, const float* legendre, void* workspace, size_t workspace_bytes, float* dpred, void* stream);
 
+/* The inverse transform, csrc/gw_sht.hip: torch_harmonics.InverseRealSHT(nlat, nlon, lmax, mmax = lmax + 1, grid="equiangular")
+ * on the two grids GenCast's generate_isotropic_noise accepts, lmax = gw_isht_lmax: nlat when nlon = 2 nlat, nlat - 1 when
+ * nlon = 2 (nlat - 1), 0 for any other shape.
+ *   coeffs     interleaved complex64 [fields, lmax, mmax] (what torch.view_as_real shows).  The imaginary parts of the orders
+ *              m = 0 and m = nlon / 2 are ignored, as irfft ignores them.
+ *   synthesis  [2 Mp, nlon], Mp = mmax rounded up to 64: row c * Mp + m holds w_m cos(2 pi m j / nlon) for c = 0 and
+ *              -w_m sin(...) for c = 1, w_0 = w_{nlon / 2} = 1 and w_m = 2 otherwise; the other rows are zero
+ *   legendre   gw_isht_legendre_floats floats: order m starts at (m * lmax - m (m - 1) / 2) * nlat and holds the rows
+ *              l = m .. lmax - 1 of Pbar_l^m(cos theta_k), nlat floats each (no quadrature weights)
+ * out [fields / channels, nlon, nlat, channels] = scale * the transform of field b * channels + ch, written in that layout
+ * directly.  One fixed summation order per element whatever the number of fields; no atomics, no host synchronisation.  The
+ * queries need no GPU (gw_isht_workspace_bytes: 0 with the error set on bad arguments). */
+int32_t gw_isht_lmax(int32_t nlat, int32_t nlon);
+size_t gw_isht_legendre_floats(int32_t nlat, int32_t nlon);
+size_t gw_isht_workspace_bytes(int32_t fields, int32_t nlat, int32_t nlon);
+int gw_isht_forward(int32_t fields, int32_t channels, int32_t nlat, int32_t nlon, const float* coeffs, const float* synthesis,
+                    const float* legendre, float scale, void* workspace, size_t workspace_bytes, float* out, void* stream);
+
 /* =====================================================================================================================
  * Per-channel modulation of [B, C, *spatial] activations, csrc/gw_modulate.hip: StochasticDecompositionLayer
  * (graph_weather/models/layers/stochastic_decomposition.py) and FiLMApplier (layers/film.py).  A tensor is `rows` = B * C
@@ -904,6 +922,23 @@ int gw_gencast_precond_output_forward(int32_t batch, int64_t grid_rows, int32_t 
 int gw_gencast_precond_output_backward(int32_t batch, int64_t grid_rows, int32_t width, float sigma_data, const float* sigma,
                                        const float* dout, int32_t ld_dout, float* dz, int32_t ld_dz, float* dpreds, int32_t ld_dpreds,
                                        void* stream);
+/* The Sampler's state update (sampler.py): out = a x + b y + c z on n dense floats, host scalars.  A NULL operand is skipped (at
+ * least one is required); out may alias x.  An element's value does not depend on its position or on n. */
+int gw_gencast_sampler_combine(int64_t n, float a, const float* x, float b, const float* y, float c, const float* z, float* out,
+                               void* stream);
+/* WeightedMSELoss (weighted_mse_loss.py) on pred / target [batch, nlon, nlat, nvar] dense, sigma [batch] > 0:
+ * loss = sum (pred - target)^2 aw[lat] fw[var] lambda(sigma_b) / (batch nlon nlat nvar), lambda(s) = (s^2 + d^2) / (s d)^2 with
+ * d = sigma_data, area_weights [nlat] and features_weights [nvar] each optional (NULL).  Sums of slabs of 4096 elements in fp64,
+ * added by one workgroup in a fixed order; no atomics.  nan_flag[0] is set to 1 when a squared residual is NaN, else to 0.
+ * backward: dpred = dloss[0] * d loss / d pred.  gw_gencast_weighted_mse_workspace_bytes: host-side query (0 with the error set
+ * on bad arguments). */
+size_t gw_gencast_weighted_mse_workspace_bytes(int32_t batch, int32_t nlon, int32_t nlat, int32_t nvar);
+int gw_gencast_weighted_mse_forward(int32_t batch, int32_t nlon, int32_t nlat, int32_t nvar, float sigma_data, const float* pred,
+                                    const float* target, const float* sigma, const float* area_weights, const float* features_weights,
+                                    void* workspace, size_t workspace_bytes, float* loss, int32_t* nan_flag, void* stream);
+int gw_gencast_weighted_mse_backward(int32_t batch, int32_t nlon, int32_t nlat, int32_t nvar, float sigma_data, const float* pred,
+                                     const float* target, const float* sigma, const float* area_weights, const float* features_weights,
+                                     const float* dloss, float* dpred, void* stream);
 /* TransformerConv's beta gate: g[r] = sigmoid(w_a . out[r] + w_b . x_r[r] + w_c . (out[r] - x_r[r])), w = [w_a | w_b | w_c]
  * (lin_beta.weight, 3 width floats), y[r] = g x_r[r] + (1 - g) out[r]; gate [rows] keeps g for the backward.  Backward: d_out and
  * d_xr (each may be NULL, leading dimension ld_d) and dw [3 width], formed as partials per slab of 256 rows in
