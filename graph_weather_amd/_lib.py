@@ -57,6 +57,8 @@ EXPORTS = [
     "gw_isht_lmax", "gw_isht_legendre_floats", "gw_isht_workspace_bytes", "gw_isht_forward",
     "gw_gencast_sampler_combine", "gw_gencast_weighted_mse_workspace_bytes", "gw_gencast_weighted_mse_forward",
     "gw_gencast_weighted_mse_backward",
+    "gw_cond_layernorm_fanout_forward", "gw_cond_layernorm_fanout_workspace_bytes", "gw_cond_layernorm_fanout_backward",
+    "gw_linear_gather_grouped_forward", "gw_segment_sum_rows_grouped",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -265,6 +267,13 @@ def lib():
     L.gw_linear_gather_forward.argtypes = [c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
                                            POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32), c_int32, c_void_p,
                                            c_int32, c_void_p]
+    L.gw_linear_gather_grouped_forward.restype = c_int
+    L.gw_linear_gather_grouped_forward.argtypes = [c_int64, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32,
+                                                   POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int32), POINTER(c_int32),
+                                                   POINTER(c_int32), c_int32, c_void_p, c_int32, c_void_p]
+    L.gw_segment_sum_rows_grouped.restype = c_int
+    L.gw_segment_sum_rows_grouped.argtypes = [c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                              c_int32, c_void_p]
     L.gw_add_rows.restype = c_int
     L.gw_add_rows.argtypes = [c_int64, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p]
     L.gw_gather_rows_wide.restype = c_int
@@ -440,6 +449,13 @@ def lib():
     L.gw_cond_layernorm_grouped_workspace_bytes.argtypes = [c_int64, c_int32, c_int64]
     L.gw_cond_layernorm_grouped_backward.restype = c_int
     L.gw_cond_layernorm_grouped_backward.argtypes = [c_int64, c_int32, c_int32, c_int64] + [c_void_p, c_int32] * 4 + [
+        c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]
+    L.gw_cond_layernorm_fanout_forward.restype = c_int
+    L.gw_cond_layernorm_fanout_forward.argtypes = [c_int64, c_int32, c_int32, c_int64, c_int32] + [c_void_p, c_int32] * 4 + [c_void_p]
+    L.gw_cond_layernorm_fanout_workspace_bytes.restype = c_size_t
+    L.gw_cond_layernorm_fanout_workspace_bytes.argtypes = [c_int64, c_int32, c_int64, c_int32]
+    L.gw_cond_layernorm_fanout_backward.restype = c_int
+    L.gw_cond_layernorm_fanout_backward.argtypes = [c_int64, c_int32, c_int32, c_int64, c_int32] + [c_void_p, c_int32] * 4 + [
         c_void_p, c_size_t, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p]
     L.gw_gencast_precond_input_forward.restype = c_int
     L.gw_gencast_precond_input_forward.argtypes = [c_int32, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p] + [

@@ -22,6 +22,9 @@
 //   cln_*_kernel         ConditionalLayerNorm: act(scale[g] o LN(x[r]) + bias[g]) (LN without affine, eps 1e-5), one wave per row;
 //                        g = r / rows_per_group (1: a scale and bias row per row).  Grouped gradient of scale and bias: per-slab
 //                        partials (256 rows of one group, one thread per column, rows in order) added in slab order
+//   cln_fan_*_kernel     the fan-out form for an ensemble (B samples x N members): one wave per row of x [B M, W] forms the statistics
+//                        once and writes the row's N conditioned outputs [B N M, W]; backward: dx summed over the members in member
+//                        order by the owning wave, the gradients of scale and bias [B N, W] through the slab partials above
 //   precond_*_kernel     the Denoiser's preconditioning (Karras et al. 2022) as row kernels: the encoder's grid input rows
 //                        (c_in(sigma_b) Z | X | static grid features) with c_noise, and c_skip(sigma_b) Z + c_out(sigma_b) preds
 //   gate_*_kernel        TransformerConv's beta gate: g = sigmoid(w_a.out + w_b.x_r + w_c.(out - x_r)), y = g x_r + (1 - g) out; the
@@ -619,19 +622,23 @@ __global__ __launch_bounds__(256) void cln_bwd_kernel(long long rows, int width,
   }
 }
 
-// part[group][slab][2][width]: one thread per column walks the rows of one slab of one group in order
+// part[group][slab][2][width]: one thread per column walks the rows of one slab of one group in order.  fan > 0 (fan-out form):
+// rows counts the rows of dout, group g = (sample, member) = (g / fan, g % fan) reads the x rows and statistics of its sample.
 __global__ __launch_bounds__(256) void cln_cols_kernel(long long rows, int width, int act, long long rpg, const float* __restrict__ x,
                                                        long long ld_x, const float* __restrict__ scale, long long ld_s,
                                                        const float* __restrict__ bias, long long ld_b, const float* __restrict__ dout,
-                                                       long long ld_do, const float* __restrict__ stats, float* __restrict__ part) {
+                                                       long long ld_do, const float* __restrict__ stats, float* __restrict__ part,
+                                                       long long fan) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= width) return;
   const long long g = blockIdx.z, g0 = g * rpg, g1 = g0 + rpg < rows ? g0 + rpg : rows;
   const long long r0 = g0 + (long long)blockIdx.y * kGateSlab, r1 = r0 + kGateSlab < g1 ? r0 + kGateSlab : g1;
   const float sc = ldg1(scale + g * ld_s + c), bi = ldg1(bias + g * ld_b + c);
   double a = 0.0, b = 0.0;  // (fp64 for the reason given at gate_cols_kernel)
+  const long long x_shift = fan > 0 ? g0 - (g / fan) * rpg : 0;  // dout row r pairs with x row r - x_shift
   for (long long r = r0; r < r1; ++r) {
-    const float xh = (ldg1(x + r * ld_x + c) - stats[2 * r]) * stats[2 * r + 1];
+    const long long rx = r - x_shift;
+    const float xh = (ldg1(x + rx * ld_x + c) - stats[2 * rx]) * stats[2 * rx + 1];
     const float dz = ldg1(dout + r * ld_do + c) * act_d(sc * xh + bi, act);
     a += (double)(dz * xh);
     b += (double)dz;
@@ -665,6 +672,92 @@ bool cln_grouped_ok(int64_t rows, int32_t width, int64_t rpg) {
 size_t cln_grouped_bytes(int64_t rows, int32_t width, int64_t rpg) {
   const int64_t groups = (rows + rpg - 1) / rpg, slabs = (rpg + kGateSlab - 1) / kGateSlab;
   return ((size_t)rows * 2 + (size_t)groups * (size_t)slabs * 2 * (size_t)width) * sizeof(float);
+}
+
+// ---- fan-out ConditionalLayerNorm: x [B M, W] -> out [B N M, W], out row (b, n, m) = act(scale[b N + n] o LN(x[b M + m]) + bias[b N + n]) --
+// One wave per x row: the statistics are formed once, then the wave writes the row's N outputs (lane l owns columns l + 64 j as in
+// cln_fwd_kernel, so every output is bitwise what the grouped kernel gives on x repeated per member).
+__global__ __launch_bounds__(256) void cln_fan_fwd_kernel(long long x_rows, int width, int act, long long rps, int members,
+                                                          const float* __restrict__ x, long long ld_x, const float* __restrict__ scale,
+                                                          long long ld_s, const float* __restrict__ bias, long long ld_b,
+                                                          float* __restrict__ out, long long ld_o) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= x_rows) return;
+  const long long b = r / rps, m = r - b * rps;
+  const float* xr = x + r * ld_x;
+  float mean, rstd;
+  row_stats(xr, width, lane, mean, rstd);
+  for (int c = lane; c < width; c += 64) {
+    const float xh = (ldg1(xr + c) - mean) * rstd;
+    for (int n = 0; n < members; ++n) {
+      const long long g = b * members + n;
+      stg1(out + (g * rps + m) * ld_o + c, act_f(ldg1(scale + g * ld_s + c) * xh + ldg1(bias + g * ld_b + c), act));
+    }
+  }
+}
+
+// Backward of the fan-out: dx[b M + m] = sum over the members, in member order, of what cln_bwd_kernel gives for output row
+// (b, n, m); the owning wave forms the two row sums of every member (lane n % 64 keeps member n's pair, 64 members per pass) and
+// then walks its columns once per pass - plain stores, a later pass adds to what the same lane stored.  stats [x_rows][2].
+__global__ __launch_bounds__(256) void cln_fan_bwd_kernel(long long x_rows, int width, int act, long long rps, int members,
+                                                          const float* __restrict__ x, long long ld_x, const float* __restrict__ scale,
+                                                          long long ld_s, const float* __restrict__ bias, long long ld_b,
+                                                          const float* __restrict__ dout, long long ld_do, float* dx, long long ld_dx,
+                                                          float* __restrict__ stats) {
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= x_rows) return;
+  const long long b = r / rps, m = r - b * rps;
+  const float* xr = x + r * ld_x;
+  float mean, rstd;
+  row_stats(xr, width, lane, mean, rstd);
+  if (lane == 0) stats[2 * r] = mean, stats[2 * r + 1] = rstd;
+  if (dx == nullptr) return;
+  for (int n0 = 0; n0 < members; n0 += 64) {
+    const int n1 = n0 + 64 < members ? n0 + 64 : members;
+    float my_sa = 0.f, my_sb = 0.f;
+    for (int n = n0; n < n1; ++n) {
+      const long long g = b * members + n;
+      const float* dr = dout + (g * rps + m) * ld_do;
+      float sa = 0.f, sb = 0.f;
+      for (int c = lane; c < width; c += 64) {
+        const float xh = (ldg1(xr + c) - mean) * rstd, sc = ldg1(scale + g * ld_s + c);
+        const float gg = ldg1(dr + c) * act_d(sc * xh + ldg1(bias + g * ld_b + c), act) * sc;
+        sa += gg;
+        sb = fmaf(gg, xh, sb);
+      }
+      sa = wave_sum(sa) / (float)width;
+      sb = wave_sum(sb) / (float)width;
+      if (lane == n - n0) my_sa = sa, my_sb = sb;
+    }
+    for (int c0 = 0; c0 < width; c0 += 64) {  // (a loop every lane runs: the shuffles below need the whole wave)
+      const int c = c0 + lane;
+      const bool on = c < width;
+      const float xh = on ? (ldg1(xr + c) - mean) * rstd : 0.f;
+      float acc = (on && n0 > 0) ? dx[r * ld_dx + c] : 0.f;
+      for (int n = n0; n < n1; ++n) {
+        const long long g = b * members + n;
+        const float sa = __shfl(my_sa, n - n0), sb = __shfl(my_sb, n - n0);
+        if (on) {
+          const float sc = ldg1(scale + g * ld_s + c);
+          const float gg = ldg1(dout + (g * rps + m) * ld_do + c) * act_d(sc * xh + ldg1(bias + g * ld_b + c), act) * sc;
+          acc += rstd * (gg - sa - xh * sb);
+        }
+      }
+      if (on) dx[r * ld_dx + c] = acc;
+    }
+  }
+}
+
+bool cln_fanout_ok(int64_t x_rows, int32_t width, int64_t rps, int32_t members) {
+  if (x_rows < 0 || width < 1 || rps < 1 || members < 1 || x_rows % rps != 0) return false;
+  if (x_rows >= ((int64_t)1 << 33) || x_rows * members >= ((int64_t)1 << 33)) return false;
+  return x_rows / rps * members <= 65535 && (rps + kGateSlab - 1) / kGateSlab <= 65535;
+}
+size_t cln_fanout_bytes(int64_t x_rows, int32_t width, int64_t rps, int32_t members) {
+  const int64_t groups = x_rows / rps * members, slabs = (rps + kGateSlab - 1) / kGateSlab;
+  return ((size_t)x_rows * 2 + (size_t)groups * (size_t)slabs * 2 * (size_t)width) * sizeof(float);
 }
 
 // ---- the Denoiser's preconditioning (utils/noise.py, denoiser.py): one wave per grid row, sample b = row / grid_rows --------------
@@ -1065,7 +1158,59 @@ int gw_cond_layernorm_grouped_backward(int64_t rows, int32_t width, int32_t act,
   const int slabs = (int)(((rows_per_group < rows ? rows_per_group : rows) + kGateSlab - 1) / kGateSlab);
   hipLaunchKernelGGL(cln_cols_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)slabs, (unsigned)groups), dim3(256), 0, st,
                      (long long)rows, (int)width, (int)act, (long long)rows_per_group, x, (long long)ld_x, scale, (long long)ld_scale, bias,
-                     (long long)ld_bias, dout, (long long)ld_dout, (const float*)stats, part);
+                     (long long)ld_bias, dout, (long long)ld_dout, (const float*)stats, part, 0LL);
+  if (int rc = check_launch("cln_cols_kernel launch")) return rc;
+  hipLaunchKernelGGL(cln_sum_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)groups), dim3(256), 0, st, slabs, (int)width,
+                     (const float*)part, dscale, dbias, (long long)ld_dsb);
+  return check_launch("cln_sum_kernel launch");
+}
+
+int gw_cond_layernorm_fanout_forward(int64_t x_rows, int32_t width, int32_t act, int64_t rows_per_sample, int32_t members, const float* x,
+                                     int32_t ld_x, const float* scale, int32_t ld_scale, const float* bias, int32_t ld_bias, float* out,
+                                     int32_t ld_out, void* stream) {
+  if (!x || !scale || !bias || !out || !cln_fanout_ok(x_rows, width, rows_per_sample, members) || act < GW_ACT_NONE || act > GW_ACT_SILU ||
+      ld_x < width || ld_scale < width || ld_bias < width || ld_out < width)
+    return failf(GW_E_BADARG, "gw_cond_layernorm_fanout_forward: bad arguments");
+  if (x_rows == 0) return GW_OK;
+  hipLaunchKernelGGL(cln_fan_fwd_kernel, dim3((unsigned)((x_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, (long long)x_rows,
+                     (int)width, (int)act, (long long)rows_per_sample, (int)members, x, (long long)ld_x, scale, (long long)ld_scale, bias,
+                     (long long)ld_bias, out, (long long)ld_out);
+  return check_launch("cln_fan_fwd_kernel launch");
+}
+
+size_t gw_cond_layernorm_fanout_workspace_bytes(int64_t x_rows, int32_t width, int64_t rows_per_sample, int32_t members) {
+  if (!cln_fanout_ok(x_rows, width, rows_per_sample, members) || x_rows < 1) {
+    failf(GW_E_BADARG, "gw_cond_layernorm_fanout_workspace_bytes: bad arguments");
+    return 0;
+  }
+  return cln_fanout_bytes(x_rows, width, rows_per_sample, members);
+}
+
+int gw_cond_layernorm_fanout_backward(int64_t x_rows, int32_t width, int32_t act, int64_t rows_per_sample, int32_t members, const float* x,
+                                      int32_t ld_x, const float* scale, int32_t ld_scale, const float* bias, int32_t ld_bias,
+                                      const float* dout, int32_t ld_dout, void* workspace, size_t workspace_bytes, float* dx, int32_t ld_dx,
+                                      float* dscale, float* dbias, int32_t ld_dsb, void* stream) {
+  if (!x || !scale || !bias || !dout || !workspace || (!dx && !dscale && !dbias) ||
+      !cln_fanout_ok(x_rows, width, rows_per_sample, members) || act < GW_ACT_NONE || act > GW_ACT_SILU || ld_x < width || ld_scale < width ||
+      ld_bias < width || ld_dout < width || (dx && ld_dx < width) || ((dscale || dbias) && ld_dsb < width))
+    return failf(GW_E_BADARG, "gw_cond_layernorm_fanout_backward: bad arguments");
+  if (x_rows == 0) return GW_OK;
+  if (workspace_bytes < cln_fanout_bytes(x_rows, width, rows_per_sample, members))
+    return failf(GW_E_BADARG, "gw_cond_layernorm_fanout_backward: bad arguments (workspace)");
+  float* stats = (float*)workspace;
+  float* part = stats + 2 * x_rows;
+  hipStream_t st = (hipStream_t)stream;
+  // (with dx NULL the row kernel still leaves the statistics the column pass reads)
+  hipLaunchKernelGGL(cln_fan_bwd_kernel, dim3((unsigned)((x_rows + 3) / 4)), dim3(256), 0, st, (long long)x_rows, (int)width, (int)act,
+                     (long long)rows_per_sample, (int)members, x, (long long)ld_x, scale, (long long)ld_scale, bias, (long long)ld_bias,
+                     dout, (long long)ld_dout, dx, (long long)ld_dx, stats);
+  if (int rc = check_launch("cln_fan_bwd_kernel launch")) return rc;
+  if (!dscale && !dbias) return GW_OK;
+  const int64_t groups = x_rows / rows_per_sample * members;
+  const int slabs = (int)((rows_per_sample + kGateSlab - 1) / kGateSlab);
+  hipLaunchKernelGGL(cln_cols_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)slabs, (unsigned)groups), dim3(256), 0, st,
+                     (long long)(groups * rows_per_sample), (int)width, (int)act, (long long)rows_per_sample, x, (long long)ld_x, scale,
+                     (long long)ld_scale, bias, (long long)ld_bias, dout, (long long)ld_dout, (const float*)stats, part, (long long)members);
   if (int rc = check_launch("cln_cols_kernel launch")) return rc;
   hipLaunchKernelGGL(cln_sum_kernel, dim3((unsigned)((width + 255) / 256), (unsigned)groups), dim3(256), 0, st, slabs, (int)width,
                      (const float*)part, dscale, dbias, (long long)ld_dsb);

@@ -10,6 +10,8 @@
 //   gw_add_rows                out = a + b                        (the residual add of an MLP without norm)
 //   gw_gather_rows_wide        out[b, i, :] = table[b, idx[i], :]
 //   gw_segment_sum_rows_wide   out[bo, n, :] = sum_b sum_{i in seg(n)} rows[b, perm[i], :]   (CSR walk: no atomics, one order)
+//   gw_linear_gather_grouped_forward / gw_segment_sum_rows_grouped: the two above with a share count per table - copy b reads
+//                              block b / share, a block's gradient sums its share copies in copy order
 //   ln_bwd_wide_launch / relu_mask_wide_launch: widths > 256 of gw_layernorm_backward / gw_relu_backward (gw_train.hip)
 
 #include <hip/hip_runtime.h>
@@ -36,7 +38,8 @@ constexpr int kNtKC = 16;
 constexpr int kNtLd = 20;
 
 // Row tables added to the product before the activation: out[m] += table_i[b * rows_pb_i + idx_i[k]] with (b, k) = (m / rpb, m % rpb)
-// (idx NULL: k itself; rows_pb 0: one table shared by the batch).  This is how the layer-1 split of the fused kernels
+// (idx NULL: k itself; rows_pb 0: one table shared by the batch; share s > 1: copy b reads block b / s - the copies are grouped,
+// the s members of a group read one block).  This is how the layer-1 split of the fused kernels
 // (cat[x_s, x_d, e] . W1^T = x_s.Ws^T[src] + x_d.Wd^T[dst] + e.We^T) reaches the wide path: node products are made once per
 // node and gathered per edge here, in the epilogue of the edge-level product.
 struct Addends {
@@ -46,6 +49,7 @@ struct Addends {
   const int* idx[3];
   int ld[3];
   int rows_pb[3];
+  int share[3];          // >= 1
 };
 
 template <bool ALIGNED>
@@ -131,7 +135,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(int M, int N, int K, const
         const int b = (int)(mm / ga.rows_per_batch), k = (int)(mm - (int64_t)b * ga.rows_per_batch);
         for (int a = 0; a < ga.n; ++a) {
           const int tr = ga.idx[a] != nullptr ? ldgi(ga.idx[a] + k) : k;
-          const float* row = ga.table[a] + ((size_t)b * ga.rows_pb[a] + tr) * ga.ld[a];
+          const int tb = ga.share[a] == 1 ? b : b / ga.share[a];
+          const float* row = ga.table[a] + ((size_t)tb * ga.rows_pb[a] + tr) * ga.ld[a];
 #pragma unroll
           for (int tn = 0; tn < 4; ++tn) {
             const int n = n0 + 64 * wn + 16 * tn + i;
@@ -171,7 +176,8 @@ __global__ __launch_bounds__(256) void gather_sum_kernel(int64_t rows, int width
     float v = bv;
     for (int a = 0; a < ga.n; ++a) {
       const int tr = ga.idx[a] != nullptr ? ldgi(ga.idx[a] + k) : k;
-      v += ldg1(ga.table[a] + ((size_t)b * ga.rows_pb[a] + tr) * ga.ld[a] + c);
+      const int tb = ga.share[a] == 1 ? b : b / ga.share[a];
+      v += ldg1(ga.table[a] + ((size_t)tb * ga.rows_pb[a] + tr) * ga.ld[a] + c);
     }
     if (relu) v = fmaxf(v, 0.f);
     stg1(out + (size_t)m * ldo + c, v);
@@ -324,7 +330,9 @@ __global__ __launch_bounds__(256) void gather_wide_kernel(int batch, int n_idx, 
   }
 }
 
-__global__ __launch_bounds__(256) void segment_sum_wide_kernel(int batch, int batch_out, int n_seg, int width,
+// output block bo sums the `share` consecutive input copies bo share .. bo share + share - 1 in copy order (share 1: one copy per
+// block; share = batch: one block for all)
+__global__ __launch_bounds__(256) void segment_sum_wide_kernel(int share, int batch_out, int n_seg, int width,
                                                                const float* __restrict__ rows, int ld, int rows_pb_in,
                                                                const int* __restrict__ perm, const int* __restrict__ ptr,
                                                                float* __restrict__ out, int ldo) {
@@ -334,7 +342,7 @@ __global__ __launch_bounds__(256) void segment_sum_wide_kernel(int batch, int ba
   for (int64_t o = blockIdx.x; o < total; o += gridDim.x) {
     const int bo = (int)(o / n_seg), n = (int)(o - (int64_t)bo * n_seg);
     const int i0 = ldgi(ptr + n), i1 = ldgi(ptr + n + 1);
-    const int b_lo = batch_out == 1 ? 0 : bo, b_hi = batch_out == 1 ? batch : bo + 1;
+    const int b_lo = bo * share, b_hi = b_lo + share;
     float s = 0.f;
     for (int b = b_lo; b < b_hi; ++b) {
       const float* base = rows + (size_t)b * rows_pb_in * ld + c;
@@ -416,27 +424,48 @@ int gw_linear_forward(int64_t rows, int32_t k, int32_t n, const float* x, int32_
   if (rows == 0) return GW_OK;
   Addends ga = {};
   ga.rows_per_batch = 1;
+  for (int a = 0; a < 3; ++a) ga.share[a] = 1;
+  return linear_launch(rows, k, n, x, ldx, w, ldw, bias, relu, out, ldo, ga, stream);
+}
+
+static int linear_gather(const char* bad, const char* bad_addend, int64_t rows, int32_t rows_per_batch, int32_t k, int32_t n, const float* x,
+                         int32_t ldx, const float* w, int32_t ldw, const float* bias, int32_t n_add, const float* const* add_table,
+                         const int32_t* const* add_idx, const int32_t* add_ld, const int32_t* add_rows_pb, const int32_t* add_share,
+                         int32_t relu, float* out, int32_t ldo, void* stream) {
+  if (!out || rows < 0 || k < 0 || n <= 0 || ldo < n || n_add < 0 || n_add > 3 || rows_per_batch <= 0 || (k == 0 && n_add == 0) ||
+      (k > 0 && (!x || !w || ldx < k || ldw < k)) || (n_add > 0 && (!add_table || !add_idx || !add_ld || !add_rows_pb)))
+    return failw(GW_E_BADARG, bad);
+  if (rows == 0) return GW_OK;
+  Addends ga = {};
+  ga.n = n_add;
+  ga.rows_per_batch = rows_per_batch;
+  for (int a = 0; a < 3; ++a) ga.share[a] = 1;
+  for (int a = 0; a < n_add; ++a) {
+    if (!add_table[a] || add_ld[a] < n || add_rows_pb[a] < 0 || (add_share && add_share[a] < 1)) return failw(GW_E_BADARG, bad_addend);
+    ga.table[a] = add_table[a];
+    ga.idx[a] = add_idx[a];
+    ga.ld[a] = add_ld[a];
+    ga.rows_pb[a] = add_rows_pb[a];
+    if (add_share) ga.share[a] = add_share[a];
+  }
   return linear_launch(rows, k, n, x, ldx, w, ldw, bias, relu, out, ldo, ga, stream);
 }
 
 int gw_linear_gather_forward(int64_t rows, int32_t rows_per_batch, int32_t k, int32_t n, const float* x, int32_t ldx, const float* w,
                              int32_t ldw, const float* bias, int32_t n_add, const float* const* add_table, const int32_t* const* add_idx,
                              const int32_t* add_ld, const int32_t* add_rows_pb, int32_t relu, float* out, int32_t ldo, void* stream) {
-  if (!out || rows < 0 || k < 0 || n <= 0 || ldo < n || n_add < 0 || n_add > 3 || rows_per_batch <= 0 || (k == 0 && n_add == 0) ||
-      (k > 0 && (!x || !w || ldx < k || ldw < k)) || (n_add > 0 && (!add_table || !add_idx || !add_ld || !add_rows_pb)))
-    return failw(GW_E_BADARG, "gw_linear_gather_forward: bad arguments");
-  if (rows == 0) return GW_OK;
-  Addends ga = {};
-  ga.n = n_add;
-  ga.rows_per_batch = rows_per_batch;
-  for (int a = 0; a < n_add; ++a) {
-    if (!add_table[a] || add_ld[a] < n || add_rows_pb[a] < 0) return failw(GW_E_BADARG, "gw_linear_gather_forward: bad addend");
-    ga.table[a] = add_table[a];
-    ga.idx[a] = add_idx[a];
-    ga.ld[a] = add_ld[a];
-    ga.rows_pb[a] = add_rows_pb[a];
-  }
-  return linear_launch(rows, k, n, x, ldx, w, ldw, bias, relu, out, ldo, ga, stream);
+  return linear_gather("gw_linear_gather_forward: bad arguments", "gw_linear_gather_forward: bad addend", rows, rows_per_batch, k, n, x, ldx,
+                       w, ldw, bias, n_add, add_table, add_idx, add_ld, add_rows_pb, nullptr, relu, out, ldo, stream);
+}
+
+int gw_linear_gather_grouped_forward(int64_t rows, int32_t rows_per_batch, int32_t k, int32_t n, const float* x, int32_t ldx, const float* w,
+                                     int32_t ldw, const float* bias, int32_t n_add, const float* const* add_table,
+                                     const int32_t* const* add_idx, const int32_t* add_ld, const int32_t* add_rows_pb,
+                                     const int32_t* add_share, int32_t relu, float* out, int32_t ldo, void* stream) {
+  if (n_add > 0 && !add_share) return failw(GW_E_BADARG, "gw_linear_gather_grouped_forward: bad arguments");
+  return linear_gather("gw_linear_gather_grouped_forward: bad arguments", "gw_linear_gather_grouped_forward: bad addend", rows,
+                       rows_per_batch, k, n, x, ldx, w, ldw, bias, n_add, add_table, add_idx, add_ld, add_rows_pb, add_share, relu, out,
+                       ldo, stream);
 }
 
 int gw_layernorm_forward(int64_t rows, int32_t width, const float* y, int32_t ld_y, const float* gamma, const float* beta,
@@ -475,15 +504,28 @@ int gw_gather_rows_wide(int32_t batch, int32_t n_idx, int32_t width, const float
   return check_launch("gather_wide_kernel launch");
 }
 
+static int segment_sum_launch(int32_t share, int32_t batch_out, int32_t n_seg, int32_t width, const float* rows, int32_t ld,
+                              int32_t rows_per_batch_in, const int32_t* perm, const int32_t* ptr, float* out, int32_t ldo, void* stream) {
+  const int64_t total = (int64_t)batch_out * n_seg;
+  if (total == 0) return GW_OK;
+  hipLaunchKernelGGL(segment_sum_wide_kernel, dim3(row_blocks(total), (unsigned)((width + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     share, batch_out, n_seg, width, rows, ld, rows_per_batch_in, perm, ptr, out, ldo);
+  return check_launch("segment_sum_wide_kernel launch");
+}
+
 int gw_segment_sum_rows_wide(int32_t batch, int32_t batch_out, int32_t n_seg, int32_t width, const float* rows, int32_t ld,
                              int32_t rows_per_batch_in, const int32_t* perm, const int32_t* ptr, float* out, int32_t ldo, void* stream) {
   if (!rows || !ptr || !out || batch <= 0 || n_seg < 0 || width <= 0 || ld < width || ldo < width || (batch_out != batch && batch_out != 1))
     return failw(GW_E_BADARG, "gw_segment_sum_rows_wide: bad arguments");
-  const int64_t total = (int64_t)batch_out * n_seg;
-  if (total == 0) return GW_OK;
-  hipLaunchKernelGGL(segment_sum_wide_kernel, dim3(row_blocks(total), (unsigned)((width + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     batch, batch_out, n_seg, width, rows, ld, rows_per_batch_in, perm, ptr, out, ldo);
-  return check_launch("segment_sum_wide_kernel launch");
+  return segment_sum_launch(batch_out == 1 ? batch : 1, batch_out, n_seg, width, rows, ld, rows_per_batch_in, perm, ptr, out, ldo, stream);
+}
+
+int gw_segment_sum_rows_grouped(int32_t batch, int32_t share, int32_t n_seg, int32_t width, const float* rows, int32_t ld,
+                                int32_t rows_per_batch_in, const int32_t* perm, const int32_t* ptr, float* out, int32_t ldo, void* stream) {
+  if (!rows || !ptr || !out || batch <= 0 || share <= 0 || batch % share != 0 || n_seg < 0 || width <= 0 || ld < width || ldo < width ||
+      rows_per_batch_in < 0)
+    return failw(GW_E_BADARG, "gw_segment_sum_rows_grouped: bad arguments");
+  return segment_sum_launch(share, batch / share, n_seg, width, rows, ld, rows_per_batch_in, perm, ptr, out, ldo, stream);
 }
 
 }  // extern "C"

@@ -466,6 +466,18 @@ int gw_gather_rows_wide(int32_t batch, int32_t n_idx, int32_t width, const float
                         const int32_t* idx, float* out, int32_t ldo, void* stream);
 int gw_segment_sum_rows_wide(int32_t batch, int32_t batch_out, int32_t n_seg, int32_t width, const float* rows, int32_t ld,
                              int32_t rows_per_batch_in, const int32_t* perm, const int32_t* ptr, float* out, int32_t ldo, void* stream);
+/* The two calls above for copies that come in groups (B samples x N members, copy c = b N + n): every table has a share count
+ * s_i >= 1 and copy c reads block c / s_i (s_i 1: one block per copy; s_i = N: one block per sample; rows_pb_i 0: one block for
+ * all) - gw_linear_gather_forward is the case of every s_i = 1.  gw_segment_sum_rows_grouped is the gradient of such a table:
+ * out [batch / share, n_seg, width], block g the sum of copies g share .. g share + share - 1 in copy order, each walked in CSR
+ * order (batch a multiple of share); gw_segment_sum_rows_wide is share = 1 (batch_out = batch) and share = batch (batch_out = 1),
+ * with the same bits. */
+int gw_linear_gather_grouped_forward(int64_t rows, int32_t rows_per_batch, int32_t k, int32_t n, const float* x, int32_t ldx, const float* w,
+                                     int32_t ldw, const float* bias, int32_t n_add, const float* const* add_table,
+                                     const int32_t* const* add_idx, const int32_t* add_ld, const int32_t* add_rows_pb,
+                                     const int32_t* add_share, int32_t relu, float* out, int32_t ldo, void* stream);
+int gw_segment_sum_rows_grouped(int32_t batch, int32_t share, int32_t n_seg, int32_t width, const float* rows, int32_t ld,
+                                int32_t rows_per_batch_in, const int32_t* perm, const int32_t* ptr, float* out, int32_t ldo, void* stream);
 
 /* =====================================================================================================================
  * PhysicalConstraintLayer (graph_weather/models/layers/constraint_layer.py) behind the decoder (forecast.py:234-246),
@@ -904,6 +916,21 @@ int gw_cond_layernorm_grouped_backward(int64_t rows, int32_t width, int32_t act,
                                        const float* scale, int32_t ld_scale, const float* bias, int32_t ld_bias, const float* dout,
                                        int32_t ld_dout, void* workspace, size_t workspace_bytes, float* dx, int32_t ld_dx, float* dscale,
                                        float* dbias, int32_t ld_dsb, void* stream);
+/* The fan-out form, where one row turns into `members` conditioned rows (an ensemble: B samples x N members): x [B M, width] with
+ * M = rows_per_sample (x_rows = B M), scale and bias [B N, width], out [B N M, width]; output row (b, n, m) normalises x row (b, m)
+ * and applies row b N + n of scale and bias.  The statistics are formed once per x row by the wave that owns it, which writes the
+ * row's N outputs; the forward gives bitwise what gw_cond_layernorm_grouped_forward gives on x repeated per member.  Backward: dout
+ * [B N M, width]; dx [B M, width] is the sum over the members in member order, formed by the owning wave with plain stores; dscale
+ * and dbias [B N, width] through slab partials added in slab order as above (workspace: gw_cond_layernorm_fanout_workspace_bytes).
+ * No atomics.  At most 65535 (sample, member) pairs. */
+int gw_cond_layernorm_fanout_forward(int64_t x_rows, int32_t width, int32_t act, int64_t rows_per_sample, int32_t members, const float* x,
+                                     int32_t ld_x, const float* scale, int32_t ld_scale, const float* bias, int32_t ld_bias, float* out,
+                                     int32_t ld_out, void* stream);
+size_t gw_cond_layernorm_fanout_workspace_bytes(int64_t x_rows, int32_t width, int64_t rows_per_sample, int32_t members);
+int gw_cond_layernorm_fanout_backward(int64_t x_rows, int32_t width, int32_t act, int64_t rows_per_sample, int32_t members, const float* x,
+                                      int32_t ld_x, const float* scale, int32_t ld_scale, const float* bias, int32_t ld_bias,
+                                      const float* dout, int32_t ld_dout, void* workspace, size_t workspace_bytes, float* dx, int32_t ld_dx,
+                                      float* dscale, float* dbias, int32_t ld_dsb, void* stream);
 /* The Denoiser's preconditioning (denoiser.py, utils/noise.py; Karras et al. 2022) on rows r = b grid_rows + g of `batch` samples,
  * sigma [batch] > 0, the coefficients formed in float32 in the reference's order of operations from sigma and d = sigma_data > 0:
  * c_in = 1 / sqrt(sigma^2 + d^2), c_skip = d^2 / (sigma^2 + d^2), c_out = sigma d / sqrt(sigma^2 + d^2), c_noise = 1/4 log sigma.
