@@ -362,7 +362,12 @@ template <typename A>
 void fill_tile_schedule(A& a, int tiles, int passes) {
   fill_chunk_switches(a, 0);
   static const int stagger_override = GW_TUNE("GW_STAGGER", -1);
-  a.stagger = stagger_override >= 0 ? stagger_override * passes : 2 * passes + 2;
+  static const int stagger_max_tiles = GW_TUNE("GW_STAGGER_MAX_TILES", 0);  // > 0: GW_STAGGER applies to launches of at most that many tiles
+  const bool overridden = stagger_override >= 0 && (stagger_max_tiles <= 0 || tiles <= stagger_max_tiles);
+  // No start-up delay at any launch size ("fp32 forward: no start-up stagger"): on today's kernels, with
+  // two chains sharing the chip, workgroups 256..511 sleeping for 2 passes + 2 units of 8 k cycles cost the 1 degree batch-2
+  // step 0.14 ms and the batch-8 shard 0.14 ms.  The mechanism stays for tuning builds (GW_STAGGER units per pass).
+  a.stagger = overridden ? stagger_override * passes : 0;
   if (tiles <= 256) a.stagger = 0;
   static const int xcd_map = GW_TUNE("GW_XCD_MAP", 1);  // 0: workgroup i takes tile i (A/B measurements)
   a.xcd_base = (xcd_map != 0 && tiles >= 64) ? tiles / 8 : 0;

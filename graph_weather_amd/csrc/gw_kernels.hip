@@ -281,6 +281,8 @@ __global__ __launch_bounds__(kThreads, 2) void chain_kernel(const ChainArgs a) {
   // in lockstep - both gathering, then both queueing on the matrix pipe - so neither hides the other's memory
   // phase (measured: MFMA busy 57 %).  Delaying the second batch of 256 workgroups by about half a tile puts the
   // pair on each CU in anti-phase: one gathers / normalises / scatters while the other owns the matrix pipe.
+  // (Measured on the first edge_kernel.  On today's kernels the delay costs more than it gives at every launch size measured:
+  // the host sets stagger = 0 unless a tuning build asks for one - launch_chain, gw_edge_common.hpp: fill_tile_schedule.)
   if (a.stagger > 0 && (blockIdx.x >> 8) == 1) {  // only the second batch of the first wave: later workgroups start when a slot frees up, already out of phase
     for (int i = 0; i < a.stagger; ++i) __builtin_amdgcn_s_sleep(127);
   }
@@ -922,11 +924,15 @@ int launch_chain(K kernel, ChainArgs& a, void* stream, int grid_y = 1, int kind 
       g_stagger_override = GW_TUNE("GW_STAGGER", -1);
       env_read = true;
     }
-    // number of 256-K passes this launch runs per tile -> about half a tile of delay (8k-cycle sleeps)
+    // number of 256-K passes this launch runs per tile: GW_STAGGER (tuning builds) counts 8k-cycle sleeps per pass.  The rule
+    // of gw_edge_common.hpp: fill_tile_schedule - no start-up delay unless a tuning build asks for one.
     int passes = 1 + a.n_mid;
     for (int i = 0; i < 3; ++i) passes += (a.seg_k[i] > 0 && !a.seg_proj[i]) ? 1 : 0;
-    a.stagger = g_stagger_override >= 0 ? g_stagger_override * passes : 2 * passes + 2;
-    if ((a.n_cols + kColsPerWG - 1) / kColsPerWG <= 256) a.stagger = 0;
+    const int tiles = (a.n_cols + kColsPerWG - 1) / kColsPerWG;
+    static const int stagger_max_tiles = GW_TUNE("GW_STAGGER_MAX_TILES", 0);  // > 0: GW_STAGGER applies up to that many tiles
+    const bool overridden = g_stagger_override >= 0 && (stagger_max_tiles <= 0 || tiles <= stagger_max_tiles);
+    a.stagger = overridden ? g_stagger_override * passes : 0;
+    if (tiles <= 256) a.stagger = 0;
   }
   static DeviceOnce once;  // per template instantiation and device
   if (once.first()) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
