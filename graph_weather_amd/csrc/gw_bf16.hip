@@ -20,10 +20,10 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "gw_device.hpp"
-#include "gw_internal.hpp"
+#include "gw_chain16_common.hpp"
 
 using namespace gw;
+using namespace gw::chain16;
 
 #ifdef GW_TUNING
 #define GW_TUNE16(a) ((a).tune16)
@@ -33,43 +33,20 @@ using namespace gw;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // A workgroup is NW waves x NG 16-column groups per wave.  4 x 2 (128 columns, one wave per SIMD, ~450 registers: every A
 // fragment read from LDS feeds two MFMAs) is the form of the general kernels; the row-wise launches of the fused forward are
 // bound by their row loads / stores, which one lock-stepped workgroup per CU cannot overlap with anything, and run as 4 x 1
 // (64 columns, <= 256 registers, TWO workgroups per CU: twice the weight DMA and LDS reads per column, but one workgroup's
 // row traffic under the other's MFMA phases - measured 14-30 % faster; 8 x 1 in one workgroup sits between).
 constexpr int kBufBytes = 32768;            // one weight chunk buffer (2 K-steps x 16 tiles x 1 KiB)
-constexpr int kStageLd16 = 260;
-constexpr int kStageFloats16 = 64 * kStageLd16;
 constexpr int kLdsWeights = 2 * kBufBytes;  // double buffered
-constexpr int kLdsEdge = kLdsWeights + (kStageFloats16 + 64) * 4;
-
-template <int N>
-__device__ __forceinline__ void wait_vm16() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void lds_barrier16() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// DMA `bytes` (multiple of 1 KiB) of the packed weight stream into LDS at byte offset lds_off; pieces round-robin
-// over the 4 waves.
-template <int NW>
-__device__ __forceinline__ void issue_bytes(const char* __restrict__ g, int bytes, unsigned lds_off, int lane, int wave) {
-  const int npieces = bytes >> 10;
-  for (int p = wave; p < npieces; p += NW)
-    glds16_asm_s((const float*)(g + (size_t)p * 1024), (unsigned)lane * 16u,
-                 __builtin_amdgcn_readfirstlane(lds_off + (unsigned)p * 1024u));
-}
+constexpr int kLdsEdge = kLdsWeights + (kStageFloats + 64) * 4;
 
 __device__ __forceinline__ bf16x8 pack8(f32x4 lo, f32x4 hi) {
   bf16x8 r;
   r[0] = (__bf16)lo.x; r[1] = (__bf16)lo.y; r[2] = (__bf16)lo.z; r[3] = (__bf16)lo.w;
   r[4] = (__bf16)hi.x; r[5] = (__bf16)hi.y; r[6] = (__bf16)hi.z; r[7] = (__bf16)hi.w;
   return r;
-}
-__device__ __forceinline__ f32x4 relu4(f32x4 v) {
-  return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
 }
 // layer-1 node products as fp16 rows (GW_LAYOUT_ROWS_F16): 11 significant bits in front of the consumer's bf16 rounding of
 // the layer-1 activations; clamped to the fp16 range (an overflow would turn into inf, then NaN under LayerNorm)
@@ -96,8 +73,8 @@ __device__ __forceinline__ void pass16(f32x4 (&acc)[NG][NT], const bf16x8 (&bin)
     constexpr int dummy = 0;
     (void)dummy;
     const int steps_c = (KS - c * CS) < CS ? (KS - c * CS) : CS;
-    wait_vm16<0>();
-    if (!(tune & 4)) lds_barrier16();  // chunk c has landed for every wave; nobody still reads the other buffer
+    wait_vm<0>();
+    if (!(tune & 4)) lds_barrier();  // chunk c has landed for every wave; nobody still reads the other buffer
     if (!(tune & 1)) {
       if (c + 1 < NCH) {
         const int sn = (KS - (c + 1) * CS) < CS ? (KS - (c + 1) * CS) : CS;
@@ -148,63 +125,16 @@ __device__ __forceinline__ void pass16(f32x4 (&acc)[NG][NT], const bf16x8 (&bin)
   }
 }
 
-template <int NG, int NT>
-__device__ __forceinline__ void init_bias16(f32x4 (&acc)[NG][NT], const float* __restrict__ bias, int q) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const f32x4 bv = bias ? ldg4(bias + 16 * t + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g][t] = bv;
-  }
-}
-
 // bin[s] <- bf16(row[k(s,q,i)]) for a raw operand row (valid features [0, kvalid))
 template <int KS, bool FULL, int DEPTH = 4>
 __device__ __forceinline__ void load_raw16(bf16x8 (&bin)[KS], const float* __restrict__ row, int kvalid, int q) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  const bool pairs = !FULL && (kvalid & 1) == 0 && ((size_t)row & 7) == 0;
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    f32x4 lo, hi;
-    if (FULL) {
-      lo = ldg4(row + 32 * s + 4 * q);
-      hi = ldg4(row + 32 * s + 16 + 4 * q);
-    } else if (pairs) {
-      // rows of an even number of floats at an 8-byte aligned base (the 102 input features of the node encoder: 408-byte rows):
-      // 8-byte loads - half the load instructions of the scalar form, which is what this launch's input phase is made of
-#pragma unroll
-      for (int r = 0; r < 4; r += 2) {
-        const int k0 = 32 * s + 4 * q + r, k1 = k0 + 16;
-        const f32x2 a = k0 < kvalid ? *(const GW_AS1 f32x2*)(row + k0) : f32x2{0.f, 0.f};
-        const f32x2 b = k1 < kvalid ? *(const GW_AS1 f32x2*)(row + k1) : f32x2{0.f, 0.f};
-        lo[r] = a.x;
-        lo[r + 1] = a.y;
-        hi[r] = b.x;
-        hi[r + 1] = b.y;
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int k0 = 32 * s + 4 * q + r, k1 = k0 + 16;
-        lo[r] = k0 < kvalid ? ldg1(row + k0) : 0.f;
-        hi[r] = k1 < kvalid ? ldg1(row + k1) : 0.f;
-      }
-    }
-    bin[s] = pack8(lo, hi);
-    // at most 2 DEPTH row pieces in flight per group (DEPTH = 4 where registers are scarce: one wave per SIMD with two groups)
-    if ((s & (DEPTH - 1)) == DEPTH - 1) __builtin_amdgcn_sched_barrier(0);
-  }
+  load_raw_steps<KS, FULL, DEPTH>(row, kvalid, q, [&](int s, f32x4 lo, f32x4 hi) { bin[s] = pack8(lo, hi); });
 }
 
 template <int NT>
 __device__ __forceinline__ void relu_to_bin(bf16x8 (&bin)[NT / 2], const f32x4 (&acc)[NT]) {
 #pragma unroll
   for (int s = 0; s < NT / 2; ++s) bin[s] = pack8(relu4(acc[2 * s]), relu4(acc[2 * s + 1]));
-}
-
-__device__ __forceinline__ const float* operand_row16(const float* ptr, const int* idx, int rows_pb, int ld, int b, int k) {
-  const int r = idx ? ldgi(idx + k) : k;
-  return ptr + ((size_t)b * (size_t)rows_pb + (size_t)r) * (size_t)ld;
 }
 
 // K1S: 32-wide K-steps of a raw layer-1 operand (8: k = 256, 4: k <= 128, 1: k <= 32); HT / OT: hidden / output row tiles.
@@ -226,37 +156,15 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
   // (measured and dropped: per-batch tiles walked batch-innermost and XCD-aware, so that batch-shared operand rows come from the
   // XCD's L2 - the head launch 1.19 -> 1.18 ms, the mesh-sized node updates 0.168 -> 0.175 ms)
 
-  int cc[NG], bb[NG], kk[NG];
-  bool valid[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const int c_raw = tile_c0 + g * (NW * 16) + wave * 16 + j;
-    valid[g] = c_raw < a.n_cols;
-    cc[g] = valid[g] ? c_raw : a.n_cols - 1;
-    bb[g] = cc[g] / a.cols_per_batch;
-    kk[g] = cc[g] - bb[g] * a.cols_per_batch;
-  }
+  GW_CHAIN16_COLUMN_COORDS(NW, NG)
 
-  bool on[3], prj[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    on[i] = (i < NSEG) && (a.seg_k[i] > 0) && (a.seg_proj[i] == 0);
-    prj[i] = (i < NSEG) && (a.seg_k[i] > 0) && (a.seg_proj[i] != 0);
-  }
-  const char* w1[3] = {(const char*)a.w1[0], (const char*)a.w1[1], (const char*)a.w1[2]};
-  if (SINGLE) w1[0] = (const char*)a.proj_w[blockIdx.y];
-  const char* w_mid = (const char*)a.w_mid;
-  const char* w_out = (const char*)a.w_out;
+  GW_CHAIN16_OPERAND_SCHEDULE(NSEG, SINGLE)
   constexpr int K1_CS = H_CS;
   constexpr int K1FIRST = (K1S < K1_CS ? K1S : K1_CS) * H_STEP;
   const char* after_l1 = SINGLE ? nullptr : (a.n_mid > 0 ? w_mid : w_out);
   const int after_l1_bytes = SINGLE ? 0 : (a.n_mid > 0 ? H_CS * H_STEP : O_CS * O_STEP);
   int parity = 0;
-  {
-    const char* first = on[0] ? w1[0] : (on[1] ? w1[1] : (on[2] ? w1[2] : after_l1));
-    const int first_bytes = (on[0] || on[1] || on[2]) ? K1FIRST : after_l1_bytes;
-    issue_bytes<NW>(first, first_bytes, 0u, lane, wave);
-  }
+  issue_first_chunk<NW>(on, w1, K1FIRST, after_l1, after_l1_bytes, lane, wave);
 
   // ---- layer 1 ----
   // One accumulator array and one B-operand array serve every layer (the output layer gets its own accumulator only
@@ -265,7 +173,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
   constexpr bool SHARE_ACC = (OT == HT);
   f32x4 acc[NG][HT];
   bf16x8 bin[NG][BKS];
-  init_bias16<NG, HT>(acc, a.b1, q);
+  init_bias<NG, HT>(acc, a.b1, q);
   {
 #pragma unroll
     for (int i = 0; i < NSEG; ++i) {
@@ -279,7 +187,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
 #pragma unroll
             for (int s = 0; s < (K1S == 8 ? 8 : 0); ++s) bin[g][s] = *(const GW_AS1 bf16x8*)(rowb + 32 * s + 8 * q);
           } else {
-            const float* row = operand_row16(a.seg_ptr[i], a.seg_idx[i], a.seg_rows_pb[i], a.seg_ld[i], bb[g], kk[g]);
+            const float* row = operand_row(a.seg_ptr[i], a.seg_idx[i], a.seg_rows_pb[i], a.seg_ld[i], bb[g], kk[g]);
             load_raw16<K1S, K1FULL, (NG == 1 ? 8 : 4)>(reinterpret_cast<bf16x8(&)[K1S]>(bin[g]), row, a.seg_k[i], q);
           }
           __builtin_amdgcn_sched_barrier(0);
@@ -306,7 +214,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
               if ((t & 7) == 7) __builtin_amdgcn_sched_barrier(0);
             }
           } else {
-            const float* row = operand_row16(a.seg_ptr[i], a.seg_idx[i], a.seg_rows_pb[i], a.seg_ld[i], bb[g], kk[g]);
+            const float* row = operand_row(a.seg_ptr[i], a.seg_idx[i], a.seg_rows_pb[i], a.seg_ld[i], bb[g], kk[g]);
 #pragma unroll
             for (int t = 0; t < HT; ++t) {
               acc[g][t] += ldg4(row + 16 * t + 4 * q);
@@ -327,7 +235,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
 #pragma unroll
       for (int g = 0; g < NG; ++g) relu_to_bin<HT>(reinterpret_cast<bf16x8(&)[HKS]>(bin[g]), acc[g]);
       __builtin_amdgcn_sched_barrier(0);
-      init_bias16<NG, HT>(acc, a.b_mid + l * (HT * 16), q);
+      init_bias<NG, HT>(acc, a.b_mid + l * (HT * 16), q);
       const bool last = (l + 1 == a.n_mid);
       const char* nx = last ? w_out : w_mid + (size_t)(l + 1) * HKS * H_STEP;
       const int nb = last ? O_CS * O_STEP : H_CS * H_STEP;
@@ -337,64 +245,19 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
 #pragma unroll
     for (int g = 0; g < NG; ++g) relu_to_bin<HT>(reinterpret_cast<bf16x8(&)[HKS]>(bin[g]), acc[g]);
     __builtin_amdgcn_sched_barrier(0);
-    init_bias16<NG, OT>(o, a.b_out, q);
+    init_bias<NG, OT>(o, a.b_out, q);
     pass16<NW, NG, HKS, BKS, OT, OTP>(o, bin, w_out, POST ? (const char*)a.proj_w[0] : (HEAD ? (const char*)a.hd_w1 : nullptr),
                               POST ? H_CS * H_STEP : (HEAD ? 2 * 8 * 1024 : 0), lds16, parity, lane, wave, GW_TUNE16(a));
   }
 
   // ---- LayerNorm over the OT*16 features of each column (eps 1e-5, biased variance), fp32 ----
   if (!SINGLE && a.gamma != nullptr) {
-    constexpr float inv_n = 1.0f / (OT * 16);
-    float mean[NG], rstd[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      float s = 0.f;
-#pragma unroll
-      for (int t = 0; t < OT; ++t) s += (o[g][t].x + o[g][t].y) + (o[g][t].z + o[g][t].w);
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      mean[g] = s * inv_n;
-      float v = 0.f;
-#pragma unroll
-      for (int t = 0; t < OT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float d = o[g][t][r] - mean[g];
-          v += d * d;
-        }
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      rstd[g] = 1.0f / sqrtf(v * inv_n + 1e-5f);
-    }
-#pragma unroll
-    for (int t = 0; t < OT; ++t) {
-      const f32x4 gm = ldg4(a.gamma + 16 * t + 4 * q);
-      const f32x4 bt = ldg4(a.beta + 16 * t + 4 * q);
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[g][t][r] = (o[g][t][r] - mean[g]) * rstd[g] * gm[r] + bt[r];
-    }
+    GW_CHAIN16_LAYERNORM(o, NG, OT, false)
   }
 
   // ---- residual ----
   if (!SINGLE && !HEAD && a.res_ptr != nullptr && !(GW_TUNE16(a) & 16)) {
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const float* rrow = operand_row16(a.res_ptr, a.res_idx, a.res_rows_pb, a.res_ld, bb[g], kk[g]);
-#pragma unroll
-      for (int t = 0; t < OT; ++t) {
-        const int f0 = 16 * t + 4 * q;
-        if (EPI == EPI_DEC) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (f0 + r < a.out_cols) o[g][t][r] += ldg1(rrow + f0 + r);
-        } else {
-          o[g][t] += ldg4(rrow + f0);
-          if ((t & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
+    GW_CHAIN16_ADD_RESIDUAL(o, NG, OT, EPI)
   }
 
   // ---- store ----
@@ -409,12 +272,8 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
           const int f0 = 16 * t + 4 * q;
           if (SINGLE && a.proj_half) {  // (out_ld counts halves)
             stg_half4((_Float16*)outp + (size_t)cc[g] * (size_t)a.out_ld + f0, o[g][t]);
-          } else if (EPI == EPI_DEC) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (f0 + r < a.out_cols) stg1(orow + f0 + r, o[g][t][r]);
           } else {
-            stg4(orow + f0, o[g][t]);
+            store_tile<EPI>(orow, f0, o[g][t], a.out_cols);
           }
         }
       }
@@ -435,45 +294,20 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
     __builtin_amdgcn_sched_barrier(0);
     constexpr int HS = 8 * 1024;  // bytes of one K-step of a packed slice with <= 8 row tiles
     f32x4 hh[NG][8];
-    init_bias16<NG, 8>(hh, a.hd_b1, q);
+    init_bias<NG, 8>(hh, a.hd_b1, q);
     pass16<NW, NG, 8, BKS, 8, 8>(hh, bin, (const char*)a.hd_w1, (const char*)a.hd_w2, 2 * HS, lds16, parity, lane, wave, GW_TUNE16(a));
 #pragma unroll
     for (int g = 0; g < NG; ++g) relu_to_bin<8>(reinterpret_cast<bf16x8(&)[4]>(bin[g]), hh[g]);
     __builtin_amdgcn_sched_barrier(0);
-    init_bias16<NG, 8>(hh, a.hd_b2, q);
+    init_bias<NG, 8>(hh, a.hd_b2, q);
     pass16<NW, NG, 4, BKS, 8, 8>(hh, bin, (const char*)a.hd_w2, (const char*)a.hd_w3, 2 * HS, lds16, parity, lane, wave, GW_TUNE16(a));
 #pragma unroll
     for (int g = 0; g < NG; ++g) relu_to_bin<8>(reinterpret_cast<bf16x8(&)[4]>(bin[g]), hh[g]);
     __builtin_amdgcn_sched_barrier(0);
     f32x4 y[NG][5];
-    init_bias16<NG, 5>(y, a.hd_b3, q);
+    init_bias<NG, 5>(y, a.hd_b3, q);
     pass16<NW, NG, 4, BKS, 5, 8>(y, bin, (const char*)a.hd_w3, nullptr, 0, lds16, parity, lane, wave, GW_TUNE16(a));
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      if (valid[g]) {
-        const float* rrow = a.res_ptr ? operand_row16(a.res_ptr, a.res_idx, a.res_rows_pb, a.res_ld, bb[g], kk[g]) : nullptr;
-        float* orow = a.out + (size_t)cc[g] * (size_t)a.out_ld;
-        // rows of an even number of floats at 8-byte aligned bases (78 outputs, 102-float feature rows): 8-byte accesses
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const bool pairs = (a.out_cols & 1) == 0 && ((size_t)orow & 7) == 0 && ((size_t)rrow & 7) == 0;
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-          const int f0 = 16 * t + 4 * q;
-          if (pairs) {
-#pragma unroll
-            for (int r = 0; r < 4; r += 2)
-              if (f0 + r < a.out_cols) {
-                const f32x2 rv = rrow ? *(const GW_AS1 f32x2*)(rrow + f0 + r) : f32x2{0.f, 0.f};
-                *(GW_AS1 f32x2*)(orow + f0 + r) = f32x2{y[g][t][r] + rv.x, y[g][t][r + 1] + rv.y};
-              }
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (f0 + r < a.out_cols) stg1(orow + f0 + r, y[g][t][r] + (rrow ? ldg1(rrow + f0 + r) : 0.f));
-          }
-        }
-      }
-    }
+    GW_CHAIN16_STORE_HEAD_ROWS(y, NG)
   }
 
   // ---- POST: the next block's layer-1 products of the new rows, while they are still in registers (see ChainArgs) ----
@@ -485,17 +319,11 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
       for (int s = 0; s < 8; ++s) bin[g][s] = pack8(o[g][2 * s], o[g][2 * s + 1]);
     __builtin_amdgcn_sched_barrier(0);
     if (a.zero_rows != nullptr) {
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-        if (valid[g]) {
-          float* zrow = a.zero_rows + (size_t)cc[g] * 256;
-#pragma unroll
-          for (int t = 0; t < 16; ++t) stg4(zrow + 16 * t + 4 * q, f32x4{0.f, 0.f, 0.f, 0.f});
-        }
+      GW_CHAIN16_ZERO_FILL(NG)
     }
 #pragma unroll 1
     for (int sl = 0; sl < a.n_post; ++sl) {
-      init_bias16<NG, HT>(acc, nullptr, q);  // (acc aliases o: the new rows have been stored and packed into bin)
+      init_bias<NG, HT>(acc, nullptr, q);  // (acc aliases o: the new rows have been stored and packed into bin)
       const char* nx = sl + 1 < a.n_post ? (const char*)a.proj_w[sl + 1] : nullptr;
       pass16<NW, NG, 8, BKS, HT, HTP>(acc, bin, (const char*)a.proj_w[sl], nx, H_CS * H_STEP, lds16, parity, lane, wave, GW_TUNE16(a));
 #pragma unroll
@@ -506,9 +334,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
 #pragma unroll
             for (int t = 0; t < HT; ++t) stg_half4(prow + 16 * t + 4 * q, acc[g][t]);
           } else {
-            float* prow = a.proj_out[sl] + (size_t)cc[g] * 256;
-#pragma unroll
-            for (int t = 0; t < HT; ++t) stg4(prow + 16 * t + 4 * q, acc[g][t]);
+            store_tiles<HT>(a.proj_out[sl] + (size_t)cc[g] * 256, acc[g], q);
           }
         }
     }
@@ -516,90 +342,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chain16_kerne
 
   // ---- segment sum over destination-sorted columns, 64 columns at a time through LDS (see gw_edge.hip) ----
   if (EPI == EPI_EDGE) {
-    float* stage = (float*)(lds16 + kLdsWeights);
-    int* gdl = (int*)(stage + kStageFloats16);
-#pragma unroll 1
-    for (int g = 0; g < NG; ++g) {
-      __syncthreads();  // previous round's readers are done
-      {
-        float* srow = stage + (wave * 16 + j) * kStageLd16 + 4 * q;
-        // (dynamic g: select the group's registers with a fully unrolled compare chain)
-#pragma unroll
-        for (int g2 = 0; g2 < NG; ++g2)
-          if (g2 == g) {
-#pragma unroll
-            for (int t = 0; t < OT; ++t) *(f32x4*)(srow + 16 * t) = o[g2][t];
-            if (q == 0) gdl[wave * 16 + j] = valid[g2] ? bb[g2] * a.agg_rows_pb + ldgi(a.agg_idx + kk[g2]) : -1;
-          }
-      }
-      __syncthreads();
-      // all 64 LDS reads first; run ends are a 64-bit scalar mask (lane i compares column i with column i + 1): the walk
-      // is straight-line code testing one bit per column (see gw_edge.hip)
-      const int f = threadIdx.x;
-      float vv[64];
-#pragma unroll
-      for (int i = 0; i < 64; ++i) vv[i] = stage[i * kStageLd16 + f];
-      const int gdv = gdl[lane];
-      const int gdn = gdl[lane < 63 ? lane + 1 : lane];
-      const unsigned long long ends = __ballot(lane == 63 || gdn != gdv);
-      // deterministic mode: carry records instead of atomics (gw_internal.hpp; same scheme as gw_edge.hip)
-      bool open_lo = true, open_hi = true;
-      float* rec = nullptr;
-      if (a.carry != nullptr) {
-        const int chunk_c0 = tile_c0 + g * 64;
-        rec = a.carry + (size_t)(chunk_c0 >> 6) * kCarryFloats;
-        const int c_prev = chunk_c0 - 1, c_next = chunk_c0 + 64;
-        int gd_prev = -2, gd_next = -2;
-        if (c_prev >= 0 && c_prev < a.n_cols) {
-          const int bp = c_prev / a.cols_per_batch;
-          gd_prev = bp * a.agg_rows_pb + ldgi(a.agg_idx + (c_prev - bp * a.cols_per_batch));
-        }
-        if (c_next < a.n_cols) {
-          const int bn = c_next / a.cols_per_batch;
-          gd_next = bn * a.agg_rows_pb + ldgi(a.agg_idx + (c_next - bn * a.cols_per_batch));
-        }
-        open_lo = gd_prev == __builtin_amdgcn_readlane(gdv, 0);
-        open_hi = gd_next == __builtin_amdgcn_readlane(gdv, 63);
-        if (f == 0 && chunk_c0 < a.n_cols) {
-          rec[512] = __int_as_float(-1);
-          rec[513] = __int_as_float(-1);
-          rec[514] = __int_as_float(0);
-        }
-      }
-      float run = 0.f;
-      bool first = true;
-#pragma unroll
-      for (int i = 0; i < 64; ++i) {
-        run += vv[i];
-        if (__builtin_expect((ends >> i) & 1ull, 0)) {
-          const int cur = __builtin_amdgcn_readlane(gdv, i);
-          if (cur >= 0) {
-            float* dstp = a.agg + (size_t)cur * 256 + f;
-            if (rec != nullptr) {
-              const bool lo = first && open_lo, hi = i == 63 && open_hi;
-              if (lo) {
-                rec[f] = run;
-                if (f == 0) {
-                  rec[512] = __int_as_float(cur);
-                  if (hi) rec[514] = __int_as_float(1);
-                }
-              } else if (hi) {
-                rec[256 + f] = run;
-                if (f == 0) rec[513] = __int_as_float(cur);
-              } else {
-                stg1(dstp, run);
-              }
-            } else if (first || i == 63) {
-              __hip_atomic_fetch_add((GW_AS1 float*)dstp, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-              stg1(dstp, run);
-            }
-          }
-          first = false;
-          run = 0.f;
-        }
-      }
-    }
+    GW_CHAIN16_SEGMENT_SUM(o, (float*)(lds16 + kLdsWeights), NW, NG, OT, 0, wave)
   }
 }
 
@@ -621,11 +364,7 @@ __global__ void pack_linear_bf16_kernel(const float* __restrict__ w, int n_out, 
 
 template <typename K>
 int launch16(K kernel, ChainArgs& a, void* stream, int grid_y, int lds_bytes, int threads = 256, int cols = 128) {
-  static DeviceOnce once;  // per template instantiation and device
-  if (once.first()) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsEdge);
-  const int grid = (a.n_cols + cols - 1) / cols;
-  hipLaunchKernelGGL(kernel, dim3(grid, grid_y), dim3(threads), lds_bytes, (hipStream_t)stream, a);
-  return check_launch("chain16_kernel launch");
+  return launch_chain16(kernel, a, stream, grid_y, lds_bytes, threads, cols, kLdsEdge, "chain16_kernel launch");
 }
 
 }  // namespace
@@ -731,14 +470,10 @@ int chain16_launch(int kind, ChainArgs& a, int k_in, int hidden, int n_out, int 
 
 extern "C" {
 
-// K-steps (32 input features each) of a packed bf16 slice: the layer-1 kernels exist for 1, 4 and 8 steps (k <= 32, k <= 128,
-// 256) and stream exactly that many, so a narrower slice is zero-padded to its variant's step count (see gw_packed_floats).
-static int packed_steps_bf16(int kseg) { return kseg <= 32 ? 1 : (kseg <= 128 ? 4 : (kseg + 31) / 32); }
-
 size_t gw_packed_bytes_bf16(int n_out, int k_lo, int k_hi) {
   const int kseg = k_hi - k_lo;
-  const int nsteps = packed_steps_bf16(kseg);
-  const int ntp = (((n_out + 15) / 16) + 3) / 4 * 4;
+  const int nsteps = packed_steps16(kseg);
+  const int ntp = padded_tiles(n_out);
   return (size_t)nsteps * ntp * 1024;
 }
 
@@ -746,8 +481,8 @@ int gw_pack_linear_bf16(const float* w, int n_out, int k_total, int k_lo, int k_
   if (!w || !out || n_out <= 0 || k_lo < 0 || k_hi <= k_lo || k_hi > k_total)
     return gw::set_error(GW_E_BADARG, "gw_pack_linear_bf16: bad arguments");
   const int kseg = k_hi - k_lo;
-  const int nsteps = packed_steps_bf16(kseg);
-  const int ntp = (((n_out + 15) / 16) + 3) / 4 * 4;
+  const int nsteps = packed_steps16(kseg);
+  const int ntp = padded_tiles(n_out);
   const size_t total = (size_t)nsteps * ntp * 512;
   int grid = (int)((total + 255) / 256);
   if (grid > 4096) grid = 4096;

@@ -30,10 +30,10 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "gw_device.hpp"
-#include "gw_internal.hpp"
+#include "gw_chain16_common.hpp"
 
 using namespace gw;
+using namespace gw::chain16;
 
 namespace {
 
@@ -131,11 +131,6 @@ __device__ __forceinline__ void issue_chunk64(const char* __restrict__ g, const 
     if ((i + 1) * NW <= NP || pc < NP)
       glds16_asm_s((const float*)(g + (size_t)pc * 1024), (unsigned)lane * 16u, __builtin_amdgcn_readfirstlane(lds0 + (unsigned)pc * 1024u));
   }
-}
-
-__device__ __forceinline__ const float* operand_row(const float* ptr, const int* idx, int rows_pb, int ld, int b, int k) {
-  const int rr = idx ? ldgi(idx + k) : k;
-  return ptr + ((size_t)b * (size_t)rows_pb + (size_t)rr) * (size_t)ld;
 }
 
 // what the two kernels share: who this wave is, where its column lives
@@ -440,22 +435,8 @@ __global__ __launch_bounds__(CG * 256, CG) void node_rs_kernel(const ChainArgs a
 // 1 KiB each = 32 KiB = one chunk.  K order k(s, q, i) = 32 s + 16 (i >> 2) + 4 q + (i & 3): K-step s of a layer's B operand is
 // split(acc[2s], acc[2s + 1]) of the layer before, so row quarter r owns K-steps 2r, 2r + 1 of the next operand.
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int kStepBytes3 = 32768;       // one K-step: hi + lo fragments of the 16 row tiles
 constexpr int kChunkBytes3 = 2 * kStepBytes3;  // one chunk buffer
-
-__device__ __forceinline__ void split8(f32x4 a, f32x4 b, bf16x8& h, bf16x8& l) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const __bf16 ha = (__bf16)a[i];
-    h[i] = ha;
-    l[i] = (__bf16)(a[i] - (float)ha);
-    const __bf16 hb = (__bf16)b[i];
-    h[4 + i] = hb;
-    l[4 + i] = (__bf16)(b[i] - (float)hb);
-  }
-}
-__device__ __forceinline__ f32x4 relu4(f32x4 v) { return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)}; }
 
 // (bh, bl)[s] <- split(row[k(s, q, i)]) of a full fp32 row
 __device__ __forceinline__ void load_slice3(bf16x8& h, bf16x8& l, const float* __restrict__ row, int s, int q) {

@@ -33,14 +33,12 @@
 #include <stdint.h>
 #include <string.h>
 
-#include "gw_device.hpp"
-#include "gw_internal.hpp"
+#include "gw_chain16_common.hpp"
 
 using namespace gw;
+using namespace gw::chain16;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // phase clocks (tuning builds only: gw_debug_timestamps + scripts/gpu_timeline_x3.py); nothing in the product build
 #ifdef GW_TUNING
@@ -53,8 +51,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // One weight chunk buffer (double buffered): 32 KiB = one K-step of 16 row tiles (hi + lo) for the 4-wave workgroups (two per
 // CU), 64 KiB = two K-steps for the 8-wave workgroup (one per CU: half the chunk hand-overs per layer)
 constexpr int buf_bytes(int nw) { return nw == 8 ? 65536 : 32768; }
-constexpr int kStageLd = 260;
-constexpr int kStageFloats = 64 * kStageLd;
 // LDS of a launch: the two weight buffers; the segment-sum stage of the edge epilogue (64 columns x 260 floats + 64 destination
 // ids per 4 waves) lies OVER them (nothing streams any more by then), so two 64-column workgroups per CU fit the 160 KiB
 constexpr int lds_bytes(int nw, bool edge) {
@@ -62,37 +58,6 @@ constexpr int lds_bytes(int nw, bool edge) {
   return edge && st > w ? st : w;
 }
 constexpr int kLdsMax = 160 * 1024;
-
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// DMA `bytes` (multiple of 1 KiB) of the packed weight stream into LDS at byte offset lds_off; pieces round-robin over the waves.
-template <int NW>
-__device__ __forceinline__ void issue_bytes(const char* __restrict__ g, int bytes, unsigned lds_off, int lane, int wave) {
-  const int npieces = bytes >> 10;
-  for (int p = wave; p < npieces; p += NW)
-    glds16_asm_s((const float*)(g + (size_t)p * 1024), (unsigned)lane * 16u,
-                 __builtin_amdgcn_readfirstlane(lds_off + (unsigned)p * 1024u));
-}
-
-// x -> (bf16(x), bf16(x - bf16(x))) for the 8 values of one B fragment
-__device__ __forceinline__ void split8(f32x4 a, f32x4 b, bf16x8& h, bf16x8& l) {
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const __bf16 ha = (__bf16)a[r];
-    h[r] = ha;
-    l[r] = (__bf16)(a[r] - (float)ha);
-    const __bf16 hb = (__bf16)b[r];
-    h[4 + r] = hb;
-    l[4 + r] = (__bf16)(b[r] - (float)hb);
-  }
-}
-__device__ __forceinline__ f32x4 relu4(f32x4 v) {
-  return f32x4{fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)};
-}
 
 // One layer pass: acc[g][t] += W[16t.., k] . x[g][k] on split operands, K = 32 KS, NT row tiles, NTP = tiles per K-step in the
 // packed stream (NT rounded up to 4).  The stream of this pass starts at gw; its first chunk has already been issued into buffer
@@ -210,49 +175,10 @@ __device__ __forceinline__ void pass_x3(f32x4 (&acc)[NG][NT], const bf16x8 (&bh)
   }
 }
 
-template <int NG, int NT>
-__device__ __forceinline__ void init_bias(f32x4 (&acc)[NG][NT], const float* __restrict__ bias, int q) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const f32x4 bv = bias ? ldg4(bias + 16 * t + 4 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int g = 0; g < NG; ++g) acc[g][t] = bv;
-  }
-}
-
 // (bh, bl)[s] <- split(row[k(s,q,i)]) for a raw operand row (valid features [0, kvalid))
 template <int KS, bool FULL, int DEPTH>
 __device__ __forceinline__ void load_raw(bf16x8 (&bh)[KS], bf16x8 (&bl)[KS], const float* __restrict__ row, int kvalid, int q) {
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
-  const bool pairs = !FULL && (kvalid & 1) == 0 && ((size_t)row & 7) == 0;
-#pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    f32x4 lo, hi;
-    if (FULL) {
-      lo = ldg4(row + 32 * s + 4 * q);
-      hi = ldg4(row + 32 * s + 16 + 4 * q);
-    } else if (pairs) {  // rows of an even number of floats at an 8-byte aligned base (102 input features): 8-byte loads
-#pragma unroll
-      for (int r = 0; r < 4; r += 2) {
-        const int k0 = 32 * s + 4 * q + r, k1 = k0 + 16;
-        const f32x2 a = k0 < kvalid ? *(const GW_AS1 f32x2*)(row + k0) : f32x2{0.f, 0.f};
-        const f32x2 b = k1 < kvalid ? *(const GW_AS1 f32x2*)(row + k1) : f32x2{0.f, 0.f};
-        lo[r] = a.x;
-        lo[r + 1] = a.y;
-        hi[r] = b.x;
-        hi[r + 1] = b.y;
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int k0 = 32 * s + 4 * q + r, k1 = k0 + 16;
-        lo[r] = k0 < kvalid ? ldg1(row + k0) : 0.f;
-        hi[r] = k1 < kvalid ? ldg1(row + k1) : 0.f;
-      }
-    }
-    split8(lo, hi, bh[s], bl[s]);
-    if ((s & (DEPTH - 1)) == DEPTH - 1) __builtin_amdgcn_sched_barrier(0);
-  }
+  load_raw_steps<KS, FULL, DEPTH>(row, kvalid, q, [&](int s, f32x4 lo, f32x4 hi) { split8(lo, hi, bh[s], bl[s]); });
 }
 
 // the next layer's B operand from this layer's accumulators (row tiles 2s, 2s+1 = K-step s)
@@ -265,11 +191,6 @@ __device__ __forceinline__ void acc_to_b(bf16x8 (&bh)[NT / 2], bf16x8 (&bl)[NT /
     else
       split8(acc[2 * s], acc[2 * s + 1], bh[s], bl[s]);
   }
-}
-
-__device__ __forceinline__ const float* operand_row(const float* ptr, const int* idx, int rows_pb, int ld, int b, int k) {
-  const int r = idx ? ldgi(idx + k) : k;
-  return ptr + ((size_t)b * (size_t)rows_pb + (size_t)r) * (size_t)ld;
 }
 
 // K1S: 32-wide K-steps of a raw layer-1 operand (8: k = 256, 4: k <= 128, 1: k <= 32); HT / OT: hidden / output row tiles.
@@ -297,16 +218,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chainx3_kerne
 #endif
   X3_STAMP(0)
 
-  int cc[NG], bb[NG], kk[NG];
-  bool valid[NG];
-#pragma unroll
-  for (int g = 0; g < NG; ++g) {
-    const int c_raw = tile_c0 + g * (NW * 16) + wave * 16 + j;
-    valid[g] = c_raw < a.n_cols;
-    cc[g] = valid[g] ? c_raw : a.n_cols - 1;
-    bb[g] = cc[g] / a.cols_per_batch;
-    kk[g] = cc[g] - bb[g] * a.cols_per_batch;
-  }
+  GW_CHAIN16_COLUMN_COORDS(NW, NG)
 
   // training (gw_activation_save): the relu output of hidden layer l of every column, as the fp32 kernels store it - the
   // backward's weight-gradient GEMMs and ReLU masks read these rows (fp32; only the products are split)
@@ -321,27 +233,14 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chainx3_kerne
       }
   };
 
-  bool on[3], prj[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    on[i] = (i < NSEG) && (a.seg_k[i] > 0) && (a.seg_proj[i] == 0);
-    prj[i] = (i < NSEG) && (a.seg_k[i] > 0) && (a.seg_proj[i] != 0);
-  }
-  const char* w1[3] = {(const char*)a.w1[0], (const char*)a.w1[1], (const char*)a.w1[2]};
-  if (SINGLE) w1[0] = (const char*)a.proj_w[blockIdx.y];
-  const char* w_mid = (const char*)a.w_mid;
-  const char* w_out = (const char*)a.w_out;
+  GW_CHAIN16_OPERAND_SCHEDULE(NSEG, SINGLE)
   constexpr int K1_CS = H_CS;
   constexpr int K1FIRST = (K1S < K1_CS ? K1S : K1_CS) * H_STEP;
   const char* after_l1 = SINGLE ? nullptr : (a.n_mid > 0 ? w_mid : w_out);
   constexpr int MID_FIRST = (HKS < H_CS ? HKS : H_CS) * H_STEP, OUT_FIRST = (HKS < O_CS ? HKS : O_CS) * O_STEP;  // first chunks
   const int after_l1_bytes = SINGLE ? 0 : (a.n_mid > 0 ? MID_FIRST : OUT_FIRST);
   int parity = 0;
-  {
-    const char* first = on[0] ? w1[0] : (on[1] ? w1[1] : (on[2] ? w1[2] : after_l1));
-    const int first_bytes = (on[0] || on[1] || on[2]) ? K1FIRST : after_l1_bytes;
-    issue_bytes<NW>(first, first_bytes, 0u, lane, wave);
-  }
+  issue_first_chunk<NW>(on, w1, K1FIRST, after_l1, after_l1_bytes, lane, wave);
   // (first-chunk sizes are whole staging groups of pass_x3: half a chunk buffer)
   static_assert(K1FIRST % (kBufBytes / 2) == 0 && MID_FIRST % (kBufBytes / 2) == 0 && OUT_FIRST % (kBufBytes / 2) == 0, "first chunks");
 
@@ -475,67 +374,14 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chainx3_kerne
     if (a.save_y != nullptr) {  // training: the pre-LayerNorm rows
 #pragma unroll
       for (int g = 0; g < NG; ++g)
-        if (valid[g]) {
-          float* srow = a.save_y + (size_t)cc[g] * (size_t)(OT * 16);
-#pragma unroll
-          for (int t = 0; t < OT; ++t) stg4(srow + 16 * t + 4 * q, o[g][t]);
-        }
+        if (valid[g]) store_tiles<OT>(a.save_y + (size_t)cc[g] * (size_t)(OT * 16), o[g], q);
     }
-    // heads and zero-padded narrow models normalise over their ln_width <= OT*16 real features (gw_mlp_weights.ln_width): the
-    // padding rows of the last Linear are zero, so they drop out of the sum and are masked out of the variance
-    const int nfeat = a.ln_width;
-    const float inv_n = 1.0f / (float)nfeat;
-    const bool full = nfeat == OT * 16;
-    float mean[NG], rstd[NG];
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      float s = 0.f;
-#pragma unroll
-      for (int t = 0; t < OT; ++t) s += (o[g][t].x + o[g][t].y) + (o[g][t].z + o[g][t].w);
-      s += __shfl_xor(s, 16);
-      s += __shfl_xor(s, 32);
-      mean[g] = s * inv_n;
-      float v = 0.f;
-#pragma unroll
-      for (int t = 0; t < OT; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float d = o[g][t][r] - mean[g];
-          v += (full || 16 * t + 4 * q + r < nfeat) ? d * d : 0.f;
-        }
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      rstd[g] = 1.0f / sqrtf(v * inv_n + 1e-5f);
-    }
-#pragma unroll
-    for (int t = 0; t < OT; ++t) {
-      const f32x4 gm = ldg4(a.gamma + 16 * t + 4 * q);
-      const f32x4 bt = ldg4(a.beta + 16 * t + 4 * q);
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) o[g][t][r] = (o[g][t][r] - mean[g]) * rstd[g] * gm[r] + bt[r];
-    }
+    GW_CHAIN16_LAYERNORM(o, NG, OT, true)
   }
 
   // ---- residual ----
   if (!SINGLE && !HEAD && a.res_ptr != nullptr) {
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      const float* rrow = operand_row(a.res_ptr, a.res_idx, a.res_rows_pb, a.res_ld, bb[g], kk[g]);
-#pragma unroll
-      for (int t = 0; t < OT; ++t) {
-        const int f0 = 16 * t + 4 * q;
-        if (EPI == EPI_DEC) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r)
-            if (f0 + r < a.out_cols) o[g][t][r] += ldg1(rrow + f0 + r);
-        } else {
-          o[g][t] += ldg4(rrow + f0);
-          if ((t & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-    }
+    GW_CHAIN16_ADD_RESIDUAL(o, NG, OT, EPI)
   }
 
   // ---- store ----
@@ -556,16 +402,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chainx3_kerne
           }
         }
 #pragma unroll
-        for (int t = 0; t < OT; ++t) {
-          const int f0 = 16 * t + 4 * q;
-          if (EPI == EPI_DEC) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (f0 + r < a.out_cols) stg1(orow + f0 + r, o[g][t][r]);
-          } else {
-            stg4(orow + f0, o[g][t]);
-          }
-        }
+        for (int t = 0; t < OT; ++t) store_tile<EPI>(orow, 16 * t + 4 * q, o[g][t], a.out_cols);
       }
     }
   }
@@ -593,31 +430,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chainx3_kerne
     f32x4 y[NG][5];
     init_bias<NG, 5>(y, a.hd_b3, q);
     pass_x3<NW, NG, 4, BKS, 5, 8, RING>(y, bh, bl, (const char*)a.hd_w3, nullptr, 0, ldsx, parity, lane, wave);
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      if (valid[g]) {
-        const float* rrow = a.res_ptr ? operand_row(a.res_ptr, a.res_idx, a.res_rows_pb, a.res_ld, bb[g], kk[g]) : nullptr;
-        float* orow = a.out + (size_t)cc[g] * (size_t)a.out_ld;
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        const bool pairs = (a.out_cols & 1) == 0 && ((size_t)orow & 7) == 0 && ((size_t)rrow & 7) == 0;
-#pragma unroll
-        for (int t = 0; t < 5; ++t) {
-          const int f0 = 16 * t + 4 * q;
-          if (pairs) {
-#pragma unroll
-            for (int r = 0; r < 4; r += 2)
-              if (f0 + r < a.out_cols) {
-                const f32x2 rv = rrow ? *(const GW_AS1 f32x2*)(rrow + f0 + r) : f32x2{0.f, 0.f};
-                *(GW_AS1 f32x2*)(orow + f0 + r) = f32x2{y[g][t][r] + rv.x, y[g][t][r + 1] + rv.y};
-              }
-          } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-              if (f0 + r < a.out_cols) stg1(orow + f0 + r, y[g][t][r] + (rrow ? ldg1(rrow + f0 + r) : 0.f));
-          }
-        }
-      }
-    }
+    GW_CHAIN16_STORE_HEAD_ROWS(y, NG)
   }
 
   // ---- POST: the next block's layer-1 products of the new rows, while they are still in registers (see ChainArgs) ----
@@ -627,13 +440,7 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chainx3_kerne
     for (int g = 0; g < NG; ++g) acc_to_b<16, false>(reinterpret_cast<bf16x8(&)[8]>(bh[g]), reinterpret_cast<bf16x8(&)[8]>(bl[g]), o[g]);
     __builtin_amdgcn_sched_barrier(0);
     if (a.zero_rows != nullptr) {
-#pragma unroll
-      for (int g = 0; g < NG; ++g)
-        if (valid[g]) {
-          float* zrow = a.zero_rows + (size_t)cc[g] * 256;
-#pragma unroll
-          for (int t = 0; t < 16; ++t) stg4(zrow + 16 * t + 4 * q, f32x4{0.f, 0.f, 0.f, 0.f});
-        }
+      GW_CHAIN16_ZERO_FILL(NG)
     }
 #pragma unroll 1
     for (int sl = 0; sl < a.n_post; ++sl) {
@@ -642,100 +449,14 @@ __global__ __launch_bounds__(NW * 64, (NW * NG == 4 ? 2 : 1)) void chainx3_kerne
       pass_x3<NW, NG, 8, BKS, HT, HTP, RING>(acc, bh, bl, (const char*)a.proj_w[sl], nx, POST_FIRST, ldsx, parity, lane, wave);
 #pragma unroll
       for (int g = 0; g < NG; ++g)
-        if (valid[g]) {
-          float* prow = a.proj_out[sl] + (size_t)cc[g] * 256;
-#pragma unroll
-          for (int t = 0; t < HT; ++t) stg4(prow + 16 * t + 4 * q, acc[g][t]);
-        }
+        if (valid[g]) store_tiles<HT>(a.proj_out[sl] + (size_t)cc[g] * 256, acc[g], q);
     }
   }
 
   X3_STAMP(5)
   // ---- segment sum over destination-sorted columns, 64 columns at a time through LDS (see gw_edge.hip) ----
   if (EPI == EPI_EDGE) {
-    // every 4 waves (256 threads = 256 features) own one 64-column chunk of the round: stage + destination ids per chunk
-    const int half = threadIdx.x >> 8;  // chunk of this thread's wave within the round (0 for 4-wave workgroups)
-    float* stage = (float*)ldsx + half * (kStageFloats + 64);  // over the weight buffers: every pass of this workgroup is complete
-    int* gdl = (int*)(stage + kStageFloats);
-#pragma unroll 1
-    for (int g = 0; g < NG; ++g) {
-      __syncthreads();  // the last pass's fragment reads / the previous round's readers are done
-      {
-        float* srow = stage + ((wave & 3) * 16 + j) * kStageLd + 4 * q;
-#pragma unroll
-        for (int g2 = 0; g2 < NG; ++g2)
-          if (g2 == g) {
-#pragma unroll
-            for (int t = 0; t < OT; ++t) *(f32x4*)(srow + 16 * t) = o[g2][t];
-            if (q == 0) gdl[(wave & 3) * 16 + j] = valid[g2] ? bb[g2] * a.agg_rows_pb + ldgi(a.agg_idx + kk[g2]) : -1;
-          }
-      }
-      __syncthreads();
-      const int f = threadIdx.x & 255;
-      float vv[64];
-#pragma unroll
-      for (int i = 0; i < 64; ++i) vv[i] = stage[i * kStageLd + f];
-      const int gdv = gdl[lane];
-      const int gdn = gdl[lane < 63 ? lane + 1 : lane];
-      const unsigned long long ends = __ballot(lane == 63 || gdn != gdv);
-      // deterministic mode: carry records instead of atomics (gw_internal.hpp; same scheme as gw_edge.hip)
-      bool open_lo = true, open_hi = true;
-      float* rec = nullptr;
-      if (a.carry != nullptr) {
-        const int chunk_c0 = tile_c0 + g * (NW * 16) + half * 64;
-        rec = a.carry + (size_t)(chunk_c0 >> 6) * kCarryFloats;
-        const int c_prev = chunk_c0 - 1, c_next = chunk_c0 + 64;
-        int gd_prev = -2, gd_next = -2;
-        if (c_prev >= 0 && c_prev < a.n_cols) {
-          const int bp = c_prev / a.cols_per_batch;
-          gd_prev = bp * a.agg_rows_pb + ldgi(a.agg_idx + (c_prev - bp * a.cols_per_batch));
-        }
-        if (c_next < a.n_cols) {
-          const int bn = c_next / a.cols_per_batch;
-          gd_next = bn * a.agg_rows_pb + ldgi(a.agg_idx + (c_next - bn * a.cols_per_batch));
-        }
-        open_lo = gd_prev == __builtin_amdgcn_readlane(gdv, 0);
-        open_hi = gd_next == __builtin_amdgcn_readlane(gdv, 63);
-        if (f == 0 && chunk_c0 < a.n_cols) {
-          rec[512] = __int_as_float(-1);
-          rec[513] = __int_as_float(-1);
-          rec[514] = __int_as_float(0);
-        }
-      }
-      float run = 0.f;
-      bool first = true;
-#pragma unroll
-      for (int i = 0; i < 64; ++i) {
-        run += vv[i];
-        if (__builtin_expect((ends >> i) & 1ull, 0)) {
-          const int cur = __builtin_amdgcn_readlane(gdv, i);
-          if (cur >= 0) {
-            float* dstp = a.agg + (size_t)cur * 256 + f;
-            if (rec != nullptr) {
-              const bool lo = first && open_lo, hi = i == 63 && open_hi;
-              if (lo) {
-                rec[f] = run;
-                if (f == 0) {
-                  rec[512] = __int_as_float(cur);
-                  if (hi) rec[514] = __int_as_float(1);
-                }
-              } else if (hi) {
-                rec[256 + f] = run;
-                if (f == 0) rec[513] = __int_as_float(cur);
-              } else {
-                stg1(dstp, run);
-              }
-            } else if (first || i == 63) {
-              __hip_atomic_fetch_add((GW_AS1 float*)dstp, run, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            } else {
-              stg1(dstp, run);
-            }
-          }
-          first = false;
-          run = 0.f;
-        }
-      }
-    }
+    GW_CHAIN16_SEGMENT_SUM(o, (float*)ldsx, NW, NG, OT, threadIdx.x >> 8, wave & 3)  // over the weight buffers
   }
 #ifdef GW_TUNING
   if (a.dbg != nullptr) {
@@ -862,11 +583,7 @@ __global__ __launch_bounds__(256, 2) void bwd_chainx3_kernel(const gw::BwdChainA
         for (int t = 0; t < HT; ++t) acc[0][t] += ldg4(drow2 + 16 * t + 4 * q);
       }
     }
-    if (valid) {
-      float* orow = a.out[p] + (size_t)c * 256;
-#pragma unroll
-      for (int t = 0; t < HT; ++t) stg4(orow + 16 * t + 4 * q, acc[0][t]);
-    }
+    if (valid) store_tiles<HT>(a.out[p] + (size_t)c * 256, acc[0], q);
     if (chain && p + 1 == a.n_chain && a.colsum != nullptr)  // (uniform) Linear_0's bias gradient: column sums of this gradient
       colsum_rows64(acc[0], valid, q, j, wave, threadIdx.x, (float*)(ldsx + 2 * buf_bytes(NW)), a.colsum, [] { lds_barrier(); });
     if (chain) {
@@ -878,11 +595,7 @@ __global__ __launch_bounds__(256, 2) void bwd_chainx3_kernel(const gw::BwdChainA
 
 template <typename K>
 int launchx3(K kernel, ChainArgs& a, void* stream, int grid_y, int lds, int threads, int cols) {
-  static DeviceOnce once;  // per template instantiation and device
-  if (once.first()) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsMax);
-  const int grid = (a.n_cols + cols - 1) / cols;
-  hipLaunchKernelGGL(kernel, dim3(grid, grid_y), dim3(threads), lds, (hipStream_t)stream, a);
-  return check_launch("chainx3_kernel launch");
+  return launch_chain16(kernel, a, stream, grid_y, lds, threads, cols, kLdsMax, "chainx3_kernel launch");
 }
 
 // one (kind, form) -> instantiation; form = 10 NW + NG.  Product build: 41 = 4 waves x 1 column group (64 columns, two workgroups
@@ -976,13 +689,10 @@ void pack_x3_item(const float* w, long long sf, long long sk, int n_out, int kse
 
 extern "C" {
 
-// K-steps (32 input features each) of a packed slice: as gw_packed_bytes_bf16 (1, 4 or k / 32 steps)
-static int packed_steps_x3(int kseg) { return kseg <= 32 ? 1 : (kseg <= 128 ? 4 : (kseg + 31) / 32); }
-
 size_t gw_packed_bytes_bf16x3(int n_out, int k_lo, int k_hi) {
   const int kseg = k_hi - k_lo;
-  const int nsteps = packed_steps_x3(kseg);
-  const int ntp = (((n_out + 15) / 16) + 3) / 4 * 4;
+  const int nsteps = packed_steps16(kseg);
+  const int ntp = padded_tiles(n_out);
   return (size_t)nsteps * ntp * 2048;
 }
 
@@ -990,7 +700,7 @@ int gw_pack_linear_bf16x3(const float* w, int n_out, int k_total, int k_lo, int 
   if (!w || !out || n_out <= 0 || k_lo < 0 || k_hi <= k_lo || k_hi > k_total)
     return gw::set_error(GW_E_BADARG, "gw_pack_linear_bf16x3: bad arguments");
   const int kseg = k_hi - k_lo;
-  gw::pack_x3_item(w + k_lo, k_total, 1, n_out, kseg, (((n_out + 15) / 16) + 3) / 4 * 4, packed_steps_x3(kseg), out, stream);
+  gw::pack_x3_item(w + k_lo, k_total, 1, n_out, kseg, padded_tiles(n_out), packed_steps16(kseg), out, stream);
   return gw::check_launch("pack_linear_x3_kernel launch");
 }
 

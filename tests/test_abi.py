@@ -49,6 +49,18 @@ def test_argument_validation_without_gpu():
     assert L.gw_packed_bytes_bf16(256, 0, 78) == 4 * 16 * 1024   # padded to the 4-step layer-1 kernel (k <= 128), not 3 steps
 
 
+@pytest.mark.parametrize("n", [5, 78, 80, 128, 256])
+@pytest.mark.parametrize("k", [1, 32, 33, 102, 128, 129, 256])
+def test_packed_bytes_of_the_16_bit_streams_closed_form(n, k):
+    """gw_packed_bytes_bf16 / _bf16x3: K-steps x row tiles per step x 1 KiB fragments (x 2: hi + lo).  The layer-1 kernels exist
+    for 1, 4 and k / 32 K-steps (k <= 32, k <= 128, wider); row tiles of 16 rows are padded to a multiple of 4."""
+    L = _lib.lib()
+    steps = 1 if k <= 32 else (4 if k <= 128 else -(-k // 32))
+    ntp = 4 * -(-(-(-n // 16)) // 4)
+    assert L.gw_packed_bytes_bf16(n, 0, k) == steps * ntp * 1024
+    assert L.gw_packed_bytes_bf16x3(n, 0, k) == 2 * steps * ntp * 1024
+
+
 def test_product_has_no_cpu_path():
     import graph_weather_amd as gw
     from graph_weather_amd.utils import regular_lat_lons
