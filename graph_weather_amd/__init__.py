@@ -21,7 +21,7 @@ from .layers import (  # noqa: F401
 )
 from .ops import BF16X3  # noqa: F401  (set_compute_dtype(model, BF16X3): split-operand products, csrc/gw_split.hip)
 from .graphcast import GraphCast, GraphCastConfig  # noqa: F401
-from .losses import AMSENormalizedLoss, NormalizedMSELoss  # noqa: F401  (AMSE: csrc/gw_sht.hip)
+from .losses import AMSENormalizedLoss, EnsembleCRPSLoss, NormalizedMSELoss  # noqa: F401  (AMSE: csrc/gw_sht.hip; CRPS: csrc/gw_crps.hip)
 from .regional import (  # noqa: F401
     BoundaryNudgingLayer,
     DynamicGraphBuilder,

@@ -59,6 +59,7 @@ EXPORTS = [
     "gw_gencast_weighted_mse_backward",
     "gw_cond_layernorm_fanout_forward", "gw_cond_layernorm_fanout_workspace_bytes", "gw_cond_layernorm_fanout_backward",
     "gw_linear_gather_grouped_forward", "gw_segment_sum_rows_grouped",
+    "gw_ensemble_crps_workspace_bytes", "gw_ensemble_crps_forward", "gw_ensemble_crps_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -95,6 +96,7 @@ class GwConstraintArgs(Structure):  # include/gw_amd.h: gw_constraint_args
 
 
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2  # GW_ACT_*
+CRPS_MEAN, CRPS_NONE = 0, 1  # GW_CRPS_*
 
 THERMAL_MAX_TAPS = 7  # GW_THERMAL_MAX_TAPS
 THERMAL_A_PLAIN, THERMAL_A_GN_RELU, THERMAL_A_DIFFUSE = 0, 1, 2  # GW_THERMAL_A_*
@@ -495,6 +497,12 @@ def lib():
     L.gw_fourier_forward.argtypes = [c_int64, c_int32, c_float, c_void_p, c_void_p, c_int32, c_void_p]
     L.gw_fourier_backward.restype = c_int
     L.gw_fourier_backward.argtypes = [c_int64, c_int32, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]
+    L.gw_ensemble_crps_workspace_bytes.restype = c_size_t
+    L.gw_ensemble_crps_workspace_bytes.argtypes = [c_int32] * 5
+    L.gw_ensemble_crps_forward.restype = c_int
+    L.gw_ensemble_crps_forward.argtypes = [c_int32] * 5 + [ctypes.c_double, c_int32] + [c_void_p] * 5 + [c_size_t, c_void_p, c_void_p]
+    L.gw_ensemble_crps_backward.restype = c_int
+    L.gw_ensemble_crps_backward.argtypes = [c_int32] * 5 + [ctypes.c_double, c_int32] + [c_void_p] * 7
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

@@ -742,6 +742,27 @@ class WeightedMSEFunction(torch.autograd.Function):
         return dpred, None, None, None, None, None
 
 
+class EnsembleCRPSFunction(torch.autograd.Function):
+    """``EnsembleCRPSLoss.forward`` (csrc/gw_crps.hip): the backward is one launch that recomputes the signs from the saved
+    operands; ``dout`` is the scalar ("mean") or the field ("none")."""
+
+    @staticmethod
+    def forward(ctx, pred, target, area_weights, features_weights, alpha, reduction):
+        out = ops.ensemble_crps_forward(pred, target, area_weights, features_weights, alpha, reduction)
+        ctx.save_for_backward(pred, target)
+        ctx.weights = (area_weights, features_weights)  # (buffers of the module, no gradient)
+        ctx.alpha, ctx.reduction = alpha, reduction
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        pred, target = ctx.saved_tensors
+        aw, fw = ctx.weights
+        dout = dout.reshape(1) if ctx.reduction == "mean" else dout
+        dpred = ops.ensemble_crps_backward(pred, target, aw, fw, dout.contiguous().float(), ctx.alpha, ctx.reduction)
+        return dpred, None, None, None, None, None
+
+
 class StochasticDecompositionFunction(torch.autograd.Function):
     """x + (alpha * style) * eps (csrc/gw_modulate.hip).  The backward regenerates eps from the 8-byte key: only the key, style
     and alpha are saved (with ``noise`` given, that tensor instead of the key).  The gradient of x is the incoming one."""

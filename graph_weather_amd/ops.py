@@ -687,6 +687,67 @@ def weighted_mse_backward(pred: torch.Tensor, target: torch.Tensor, sigma: torch
     return dpred
 
 
+CRPS_REDUCTIONS = {"mean": _lib.CRPS_MEAN, "none": _lib.CRPS_NONE}
+CRPS_REGISTER_MEMBERS = 16
+"""Ensemble sizes up to this keep the members in registers (``kCrpsRegMax`` of csrc/gw_crps.hip); larger ones, up to 1024, take the
+general kernels, which re-read the members through the cache."""
+
+
+def _crps_operands(pred, target, area_weights, features_weights, reduction):
+    _require(pred, "pred")
+    _require(target, "target")
+    if pred.dim() != 5 or tuple(target.shape) != (pred.shape[0],) + tuple(pred.shape[2:]) or target.device != pred.device:
+        raise RuntimeError("graph_weather_amd: ensemble_crps expects pred [B, N, lon, lat, C] and target [B, lon, lat, C] on one device, "
+                           "got %s and %s" % (tuple(pred.shape), tuple(target.shape)))
+    if reduction not in CRPS_REDUCTIONS:
+        raise RuntimeError("graph_weather_amd: ensemble_crps reduction must be 'mean' or 'none', got %r" % (reduction,))
+    b, n, nlon, nlat, nvar = (int(v) for v in pred.shape)
+    for name, w, size in (("area_weights", area_weights, nlat), ("features_weights", features_weights, nvar)):
+        if w is not None:
+            _require(w, name)
+            if w.numel() != size or w.device != pred.device:
+                raise RuntimeError("graph_weather_amd: %s must hold %d values on pred's device, got %d" % (name, size, w.numel()))
+    return b, n, nlon, nlat, nvar
+
+
+def ensemble_crps_forward(pred: torch.Tensor, target: torch.Tensor, area_weights: Optional[torch.Tensor],
+                          features_weights: Optional[torch.Tensor], alpha: float = 1.0, reduction: str = "mean") -> torch.Tensor:
+    """The (almost) fair CRPS of pred [B, N, lon, lat, C] against target [B, lon, lat, C] (csrc/gw_crps.hip), weighted by
+    ``area_weights`` [lat] and ``features_weights`` [C] (each may be None): the scalar mean or, with ``reduction="none"``, the
+    field [B, lon, lat, C].  Nothing of ensemble size is written."""
+    b, n, nlon, nlat, nvar = _crps_operands(pred, target, area_weights, features_weights, reduction)
+    L = _lib.lib()
+    mean = reduction == "mean"
+    ws = torch.empty(L.gw_ensemble_crps_workspace_bytes(b, n, nlon, nlat, nvar) if mean else 0, dtype=torch.uint8, device=pred.device)
+    out = torch.empty(() if mean else tuple(target.shape), dtype=torch.float32, device=pred.device)
+    with on_device_of(pred):
+        _lib.check(L.gw_ensemble_crps_forward(b, n, nlon, nlat, nvar, float(alpha), CRPS_REDUCTIONS[reduction], pred.data_ptr(),
+                                              target.data_ptr(), None if area_weights is None else area_weights.data_ptr(),
+                                              None if features_weights is None else features_weights.data_ptr(),
+                                              ws.data_ptr() if mean else None, ws.numel(), out.data_ptr(), _stream(pred)),
+                   "gw_ensemble_crps_forward")
+    return out
+
+
+def ensemble_crps_backward(pred: torch.Tensor, target: torch.Tensor, area_weights: Optional[torch.Tensor],
+                           features_weights: Optional[torch.Tensor], dout: torch.Tensor, alpha: float = 1.0,
+                           reduction: str = "mean") -> torch.Tensor:
+    """dpred of ``ensemble_crps_forward`` for the upstream gradient ``dout``: one value ("mean") or the field [B, lon, lat, C]."""
+    b, n, nlon, nlat, nvar = _crps_operands(pred, target, area_weights, features_weights, reduction)
+    _require(dout, "dout")
+    if dout.numel() != (1 if reduction == "mean" else target.numel()) or dout.device != pred.device:
+        raise RuntimeError("graph_weather_amd: ensemble_crps_backward: dout must hold %s on pred's device"
+                           % ("one value" if reduction == "mean" else "target's %d values" % target.numel()))
+    dpred = torch.empty_like(pred)
+    with on_device_of(pred):
+        _lib.check(_lib.lib().gw_ensemble_crps_backward(b, n, nlon, nlat, nvar, float(alpha), CRPS_REDUCTIONS[reduction], pred.data_ptr(),
+                                                        target.data_ptr(), None if area_weights is None else area_weights.data_ptr(),
+                                                        None if features_weights is None else features_weights.data_ptr(),
+                                                        dout.data_ptr(), dpred.data_ptr(), _stream(pred)),
+                   "gw_ensemble_crps_backward")
+    return dpred
+
+
 def _modulate_rows(x: torch.Tensor) -> Tuple[int, int, int]:
     """(rows, channels, spatial) of a dense [B, C, *spatial] tensor as csrc/gw_modulate.hip reads it."""
     rows, channels = int(x.shape[0]) * int(x.shape[1]), int(x.shape[1])

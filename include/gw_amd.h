@@ -984,6 +984,27 @@ int gw_silu_backward(int64_t n, const float* x, const float* dy, float* dx, void
 int gw_fourier_forward(int64_t rows, int32_t num_frequencies, float base_period, const float* t, float* out, int32_t ld_out, void* stream);
 int gw_fourier_backward(int64_t rows, int32_t num_frequencies, float base_period, const float* t, const float* dout, int32_t ld_dout,
                         float* dt, void* stream);
+/* EnsembleCRPSLoss: the (almost) fair continuous ranked probability score of `members` = N ensemble members against the truth, on
+ * pred [batch, N, nlon, nlat, nvar] and target [batch, nlon, nlat, nvar], dense.  Per (sample, grid point, feature)
+ *   v = (1/N) sum_i |x_i - y| - 2 c2 sum_{i<j} |x_i - x_j|,  c2 = alpha / (2 N (N-1)) + (1 - alpha) / (2 N^2)  (0 at N = 1),
+ * alpha in [0, 1]: 1 the fair score (needs N >= 2), 0 the plain ensemble score.  fp32 on direct differences, sum_i in member order,
+ * sum_{i<j} in (i, j) order; 1/N and 2 c2 are formed in double and rounded once.  N <= 16 keeps the members in registers (each value
+ * is read once); N up to 1024 re-reads them through the cache and carries the two sums in fp64.  The loss is w v, w =
+ * area_weights[lat] features_weights[var] (each optional, NULL).  reduction GW_CRPS_MEAN: out[0] = mean over batch nlon nlat nvar,
+ * from sums of slabs of 4096 elements of one sample in fp64, added by one workgroup in a fixed order (workspace:
+ * gw_ensemble_crps_workspace_bytes = 8 batch ceil(nlon nlat nvar / 4096), a host-side query, 0 with the error set on bad arguments);
+ * GW_CRPS_NONE: out [batch, nlon, nlat, nvar] = the weighted field, workspace unused (may be NULL).
+ * backward: dpred = dout * d out / d pred with sign(0) = 0 (ties contribute exactly zero), dout [1] (MEAN) or the field (NONE); the
+ * signs are recomputed from pred and target.  No atomics, no host reads. */
+#define GW_CRPS_MEAN 0
+#define GW_CRPS_NONE 1
+size_t gw_ensemble_crps_workspace_bytes(int32_t batch, int32_t members, int32_t nlon, int32_t nlat, int32_t nvar);
+int gw_ensemble_crps_forward(int32_t batch, int32_t members, int32_t nlon, int32_t nlat, int32_t nvar, double alpha, int32_t reduction,
+                             const float* pred, const float* target, const float* area_weights, const float* features_weights,
+                             void* workspace, size_t workspace_bytes, float* out, void* stream);
+int gw_ensemble_crps_backward(int32_t batch, int32_t members, int32_t nlon, int32_t nlat, int32_t nvar, double alpha, int32_t reduction,
+                              const float* pred, const float* target, const float* area_weights, const float* features_weights,
+                              const float* dout, float* dpred, void* stream);
 
 #ifdef __cplusplus
 }
