@@ -82,8 +82,21 @@ def layernorm_backward(dn: torch.Tensor, y: torch.Tensor, gamma: torch.Tensor, d
     return dy
 
 
+def _features(t: torch.Tensor) -> torch.Tensor:
+    """The 256 feature columns of a row table.  The forward reads a table through its row stride, so a table may be wider than
+    its features (padded rows); the backward's products and gathers work on the features alone."""
+    return t if t.shape[1] == 256 else t[:, :256]
+
+
+def _packed_features(t: torch.Tensor) -> torch.Tensor:
+    """... as packed 256-float rows, which gw_gather_rows reads (a copy only for a table wider than its features)."""
+    return _features(t).contiguous()
+
+
 def gather_rows(table: torch.Tensor, rows_pb: int, idx: Optional[torch.Tensor], batch: int, n_idx: int,
                 add: Optional[torch.Tensor] = None) -> torch.Tensor:
+    if table.shape[1] != 256 or table.stride(0) != 256:
+        raise RuntimeError("graph_weather_amd: gw_gather_rows reads packed 256-float rows")
     out = torch.empty((batch * n_idx, 256), dtype=torch.float32, device=table.device)
     _lib.check(_L().gw_gather_rows(batch, n_idx, table.data_ptr(), rows_pb, None if idx is None else idx.data_ptr(),
                                    None if add is None else add.data_ptr(), out.data_ptr(), _st(table)), "gw_gather_rows")
@@ -478,6 +491,7 @@ class ProjectFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *douts):
         x, W = ctx.saved_tensors
+        x = _features(x)
         gW = torch.zeros_like(W)
         dx = douts[len(ctx.slice_ids)] if ctx.passthrough else None  # gradient of the direct use of x
         if dx is not None and not ctx.needs_input_grad[3]:
@@ -586,8 +600,9 @@ class EdgeUpdateFunction(torch.autograd.Function):
                 if ctx.needs_input_grad[5 + i]:
                     dts[i] = _scatter_rows(dz0, i, plan, B, sp.rows_pb, n_rows_tab[i])
             else:  # raw rows multiplied by W0[:, lo:hi]
+                t = _features(t)
                 idx = (plan.src, plan.dst, None)[i]
-                g = t if (idx is None and sp.rows_pb > 0) else gather_rows(t, sp.rows_pb, idx, B, E)
+                g = t if (idx is None and sp.rows_pb > 0) else gather_rows(_packed_features(t), sp.rows_pb, idx, B, E)
                 gemm_tn_acc(dz0, g, gW0, c_col0=lo, colsum=gb0, x3=_x3(mlp))
                 gb0 = None
                 if ctx.needs_input_grad[5 + i]:
@@ -651,7 +666,7 @@ class NodeUpdateFunction(torch.autograd.Function):
                                      fan=fan, fan_out=fo, bias0_by_caller=True)
         W0 = params[0]
         gW0 = grads[0]  # zeroed by _mlp_chain_backward
-        gemm_tn_acc(dz0, agg, gW0, c_col0=alo, colsum=grads[1], x3=_x3(ctx.mlp))
+        gemm_tn_acc(dz0, _features(agg), gW0, c_col0=alo, colsum=grads[1], x3=_x3(ctx.mlp))
         dagg = fo[(alo, ahi)] if ctx.needs_input_grad[7] else None
         dx = None
 
@@ -660,7 +675,7 @@ class NodeUpdateFunction(torch.autograd.Function):
             return segment_sum_rows(rows, rpb, batch, 1, rpb, ident, None)
 
         if sp.mode == "raw":
-            xg = x if sp.rows_pb > 0 else gather_rows(x, 0, None, batch, rpb)
+            xg = _features(x) if sp.rows_pb > 0 else gather_rows(_packed_features(x), 0, None, batch, rpb)
             gemm_tn_acc(dz0, xg, gW0, c_col0=xlo, x3=_x3(ctx.mlp))
             if ctx.needs_input_grad[5]:
                 dx = fo[(xlo, xhi)]

@@ -1,6 +1,7 @@
 """Host logic of the MLP backward (graph_weather_amd/autograd.py: _mlp_chain_backward and the fused chain launch's extras) on the
 CPU: every C-ABI call it makes is replaced by a torch restatement of what that entry point computes (include/gw_amd.h:
-gw_mlp_ln_chain_backward, gw_gemm_f32 TN, gw_layernorm_backward, gw_gather_rows, gw_relu_backward), and the parameter / input
+gw_mlp_ln_chain_backward, gw_gemm_f32 TN, gw_layernorm_backward, gw_gather_rows, gw_relu_backward - the restatements live in
+tests/backward_restated.py, shared with tests/test_autograd_nodes_host.py), and the parameter / input
 gradients it assembles are compared with torch's fp64 autograd of the reference MLP (graph_net_block.py:45-77) for every route
 the function can take: fused launch with the LayerNorm prologue, with a gathered input gradient read in place, without
 LayerNorm, the unfused fallback; Linear_0's bias gradient from the caller's GEMM, from the chain launch, from the fallback pass;
@@ -12,99 +13,14 @@ import torch
 
 from graph_weather_amd import autograd as ag
 
+from .backward_restated import install
+
 R, B, NDST = 37, 2, 11  # edge rows per batch element, batch, destination rows
-
-
-def _ln_bwd64(dn, y, gamma):
-    yd = y.double().requires_grad_(True)
-    gd = gamma.double().requires_grad_(True)
-    bd = torch.zeros_like(gd).requires_grad_(True)
-    torch.nn.functional.layer_norm(yd, (yd.shape[1],), gd, bd, 1e-5).backward(dn.double())
-    return yd.grad, gd.grad, bd.grad
-
-
-class _Calls:
-    def __init__(self):
-        self.names = []
 
 
 @pytest.fixture
 def restated(monkeypatch):
-    calls = _Calls()
-
-    def packed_t(mlp, layer, W, lo, hi):
-        return None if getattr(mlp, "no_packs", False) else W[:, lo:hi].detach().clone()  # "stream" of the block: d @ pt
-
-    def chain_backward(d, chain, fan, ln=None, colsum=None, fan_add=None, gather=None):
-        calls.names.append("chain" + ("+ln" if ln is not None else "") + ("+gather" if gather is not None else "")
-                           + ("+colsum" if colsum is not None else ""))
-        rows = d
-        if gather is not None:
-            idx, tab_rows, add = gather
-            n = int(idx.numel())
-            b = torch.arange(int(chain[0][2].shape[0]) // n).repeat_interleave(n)
-            rows = d[b * tab_rows + idx.long().repeat(len(b) // n)]
-            if add is not None:
-                rows = rows + add
-        cur = rows.double()
-        if ln is not None:
-            y, gamma, dgamma, dbeta, dy = ln
-            gy, gg, gb = _ln_bwd64(rows, y, gamma)
-            dgamma += gg.float()
-            dbeta += gb.float()
-            dy.copy_(gy.float())
-            cur = gy
-        for pt, mask, out in chain:
-            cur = (cur @ pt.double()) * (mask > 0)
-            out.copy_(cur.float())
-        if colsum is not None:
-            colsum += cur.sum(0).float()
-        for i, (pt, out) in enumerate(fan):
-            v = cur @ pt.double()
-            extra = fan_add[i] if fan_add else None
-            if extra is ag.FAN_ADD_INPUT:
-                v = v + rows.double()
-            elif extra is not None:
-                v = v + extra.double()
-            out.copy_(v.float())
-
-    def gemm_tn_acc(a, b, c, c_col0=0, colsum=None, x3=False):
-        calls.names.append("gemm" + ("+colsum" if colsum is not None else ""))
-        c[:, c_col0:c_col0 + b.shape[1]] += (a.double().t() @ b.double()).float()
-        if colsum is not None:
-            colsum += a.double().sum(0).float()
-
-    def layernorm_backward(dn, y, gamma, dgamma, dbeta, width=0):
-        calls.names.append("ln_bwd")
-        gy, gg, gb = _ln_bwd64(dn, y, gamma)
-        dgamma += gg.float()
-        dbeta += gb.float()
-        return gy.float()
-
-    def relu_backward(dh, h, db):
-        calls.names.append("relu_bwd")
-        if h is not None:
-            dh.mul_((h > 0).float())
-        if db is not None:
-            db += dh.double().sum(0).float()
-        return dh
-
-    def input_grad(mlp, layer, d, W, lo, hi, relu_of=None):
-        calls.names.append("single")
-        out = (d.double() @ W[:, lo:hi].double()).float()
-        return out * (relu_of > 0) if relu_of is not None else out
-
-    def gather_rows(table, rows_pb, idx, batch, n_idx, add=None):
-        calls.names.append("gather")
-        b = torch.arange(batch).repeat_interleave(n_idx)
-        out = table[b * rows_pb + idx.long().repeat(batch)]
-        return out + add if add is not None else out.clone()
-
-    for name, fn in (("_packed_transposed", packed_t), ("chain_backward", chain_backward), ("gemm_tn_acc", gemm_tn_acc),
-                     ("layernorm_backward", layernorm_backward), ("relu_backward", relu_backward), ("input_grad", input_grad),
-                     ("gather_rows", gather_rows)):
-        monkeypatch.setattr(ag, name, fn)
-    return calls
+    return install(monkeypatch)
 
 
 def _case(norm: bool, seed: int):
