@@ -14,11 +14,9 @@ from typing import Tuple
 import torch
 from torch import nn
 
-from . import ops
 from .graphs import build_latent_graph, build_observation_graph
 from .layers import (AssimilatorDecoder, Feed, GraphProcessor, KeyedCache, MLP, Processor, _autograd_on, _check_native_dims, _ver,
-                     _version_key)
-from .ops import Operand
+                     cached, encoder_block_products, plans_on)
 
 try:
     from huggingface_hub import PyTorchModelHubMixin
@@ -55,10 +53,7 @@ class AssimilatorEncoder(nn.Module):
         self._cache = KeyedCache()  # "obs" (observation graph per position tensor) + the batch-independent embeddings
 
     def _latent_plan(self, device):
-        key = str(device)
-        if key not in self._dev:
-            self._dev[key] = self._lat_plan.to(device)
-        return self._dev[key]
+        return plans_on(self._dev, device, (self._lat_plan,))[0]
 
     def _observation_plan(self, lat_lon_heights: torch.Tensor, device):
         """assimilator_encoder.py:166-219, once per distinct position tensor."""
@@ -67,13 +62,8 @@ class AssimilatorEncoder(nn.Module):
         return self._cache.get("obs", key, lambda: build_observation_graph(llh.detach().cpu().numpy(), self.resolution)[2].to(device),
                                hold=lat_lon_heights)  # (the entry holds the tensor: its address stays taken)
 
-    def _cached(self, name, params, fn):
-        if _autograd_on(self):
-            return fn()
-        return self._cache.get(name, _version_key(params), fn)
-
     def latent_edge_embedding(self, plan) -> torch.Tensor:
-        return self._cached("lat_e", list(self.latent_edge_encoder.parameters()), lambda: self.latent_edge_encoder.table(plan.edge_attr))
+        return cached(self, "lat_e", list(self.latent_edge_encoder.parameters()), lambda: self.latent_edge_encoder.table(plan.edge_attr))
 
     def _is_wide(self) -> bool:
         from . import wide as wd
@@ -103,25 +93,12 @@ class AssimilatorEncoder(nn.Module):
             return x
         _check_native_dims(*self.graph_processor._dims)
         xo = self.node_encoder.table(feats)  # observation rows
-        xm = self._cached("mesh", list(self.node_encoder.parameters()), lambda: self.node_encoder.table(zeros_in))
+        xm = cached(self, "mesh", list(self.node_encoder.parameters()), lambda: self.node_encoder.table(zeros_in))
         e = self.edge_encoder.table(plan.edge_attr)  # depends on the observation positions: not cached across graphs
         blk = self.graph_processor.blocks[0]
-        train = _autograd_on(self, features)
-        M = self.num_h3
-        if train:
-            from . import autograd as ag
-
-            pd_xm = ag.project(blk.edge_model.edge_mlp, (1,), xm, M, M)[0]
-            pe = ag.project(blk.edge_model.edge_mlp, (2,), e, N, N)[0]
-            px_xm = ag.project(blk.node_model.node_mlp, (0,), xm, M, M)[0]
-        else:
-            pm_e, pm_n = blk.edge_model.edge_mlp.packed(), blk.node_model.node_mlp.packed()
-            pd_xm = ops.project_forward([pm_e.w1[1]], Operand(xm, M, 256), M, M)[0]
-            pe = ops.project_forward([pm_e.w1[2]], Operand(e, N, 256), N, N)[0]
-            px_xm = ops.project_forward([pm_n.w1[0]], Operand(xm, M, 256), M, M)[0]
-        x, _ = blk.run(B, plan, Feed(xo, N, "raw"), Feed(pd_xm, 0, "proj"), Feed(pe, 0, "proj"), e, 0, Feed(px_xm, 0, "proj"), xm,
-                       0, False, dev, tag="assimilator_encoder_edge")
-        return x
+        pd_xm, pe, px_xm, _ = encoder_block_products(blk, xm, e, _autograd_on(self, features))
+        return blk.run(B, plan, x_src=Feed(xo, N, "raw"), x_dst=Feed(pd_xm, 0, "proj"), e_in=Feed(pe, 0, "proj"),
+                       x_node=Feed(px_xm, 0, "proj"), e_res=Feed(e, 0, "raw"), x_res=Feed(xm, 0, "raw"), tag="assimilator_encoder_edge").x
 
     def forward(self, features: torch.Tensor, lat_lon_heights: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """assimilator_encoder.py:119-164: (mesh features, replicated latent edge_index, latent edge features) in

@@ -15,7 +15,7 @@ Tensors must be fp32 on a HIP device.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 from torch import nn
@@ -132,6 +132,41 @@ class Feed:
 FEED_ZERO = Feed(None, 0, "zero")
 
 
+class Post(NamedTuple):
+    """What a block's node update also produces (inference): the products of the new rows with ``w``, packed layer-1 slices of
+    the NEXT block's edge MLP; ``zero``: that block's aggregate is zero-filled on the side; ``half``: the products as fp16 rows
+    (bf16 mode, when their consumer is the bf16 edge update with resident weights: the products are gathered once per incident
+    edge, so their bytes dominate what the edge update reads)."""
+
+    w: list
+    zero: bool = False
+    half: bool = False
+
+
+class BlockOut(NamedTuple):
+    """What ``GraphNetBlock.run`` returns; None in the fields a call does not produce."""
+
+    x: torch.Tensor  # the new node rows - under ``head``: the head's output
+    e: Optional[torch.Tensor] = None  # e' (``want_edges``)
+    posts: Optional[list] = None  # the products of ``post``
+    next_agg: Optional[torch.Tensor] = None  # the zero-filled aggregate of ``post.zero``
+
+
+class SharedE0(NamedTuple):
+    """The cached forms of the batch-shared edge features of a processor's first block (``GraphProcessor._shared_e0[_seg]``)."""
+
+    pe: torch.Tensor  # We . e, the layer-1 product
+    tiles: Optional[torch.Tensor]  # e as one shared set of bf16 edge tiles
+
+
+def native_fp32_form(mlp: "MLP") -> routes.MlpForm:
+    """routes.MlpForm of an MLP for the float32 routes that need the hand-scheduled kernels' shape - native 256 widths, LayerNorm,
+    two hidden layers (n_mid 1, LayerNorm over all features); every other shape gets a form no such route accepts.  Read from
+    the module's shape alone, so asking packs no weights."""
+    native = not mlp._layout()[4] and mlp._norm() is not None and len(mlp._linears()) == 3
+    return routes.MlpForm(torch.float32, 1 if native else -1, 0 if native else -1, native)
+
+
 def set_deterministic(module: nn.Module, flag: bool = True) -> nn.Module:
     """Bitwise run-to-run reproducible forward (inference): the segment sums of every message-passing block under ``module``
     use per-tile carry records added in tile order instead of fp32 atomics, whose order is not fixed (include/gw_amd.h:
@@ -141,7 +176,7 @@ def set_deterministic(module: nn.Module, flag: bool = True) -> nn.Module:
     if flag:
         for m in blocks:
             mlp = m.edge_model.edge_mlp
-            if mlp.compute_dtype == torch.float32 and (mlp._layout()[4] or mlp._norm() is None or len(mlp._linears()) != 3):
+            if mlp.compute_dtype == torch.float32 and not native_fp32_form(mlp).has_norm:
                 # carry records exist in the hand-scheduled fp32 edge kernel (native 256 widths, LayerNorm, two hidden layers) and in
                 # the bf16 kernels; zero-padded narrow blocks, norm_type=None and deeper MLPs run on the general fp32 kernel
                 raise NotImplementedError("graph_weather_amd: deterministic segment sums are implemented for message-passing blocks "
@@ -370,37 +405,39 @@ class GraphNetBlock(nn.Module):
         self.node_model = node_model
         self.deterministic = False  # set_deterministic(): reproducible segment sums
 
-    def run(self, batch: int, plan: GraphPlan, x_src: Feed, x_dst: Feed, e_in: Feed, e_res: torch.Tensor, e_res_rows_pb: int,
-            x_node: Feed, x_res: Optional[torch.Tensor], x_res_rows_pb: int, want_edges: bool, device,
-            tag: Optional[str] = None, agg_zeroed: Optional[torch.Tensor] = None, post_w=None, post_zero: bool = False,
-            post_half: bool = False, head=None, seg=None, agg_acc: Optional[torch.Tensor] = None):
-        """One message-passing block on a shared graph: e' (optional), x' for all ``batch * plan.n_dst`` rows.
-        Inputs may be raw rows, rows pre-multiplied by their layer-1 weight slice, or zeros (see ``Feed``).
+    def run(self, batch: int, plan: GraphPlan, *, x_src: Feed, x_dst: Feed, e_in: Feed, x_node: Feed, e_res: Optional[Feed] = None,
+            x_res: Optional[Feed] = None, want_edges=False, tag: Optional[str] = None, agg_zeroed: Optional[torch.Tensor] = None,
+            post: Optional[Post] = None, head=None, seg=None, agg_acc: Optional[torch.Tensor] = None) -> BlockOut:
+        """One message-passing block on a shared graph: e' (optional), x' for all ``batch * plan.n_dst`` rows, as a ``BlockOut``.
+        ``x_src`` / ``x_dst`` / ``e_in`` (layer 1 of the edge MLP) and ``x_node`` (of the node MLP) may be raw rows, rows
+        pre-multiplied by their layer-1 weight slice, or zeros (see ``Feed``); ``e_res`` / ``x_res``: the residuals, raw rows (e as
+        rows or as bf16 edge tiles), None = no residual.
         ``agg_zeroed``: an aggregate buffer the caller has already had zero-filled (by the projection launch).
-        ``post_w`` (inference): packed layer-1 slices of the NEXT block's edge MLP - the node update multiplies the new rows by
-        them in the same launch (and zero-fills the next aggregate with ``post_zero``); returns (x', e', products, next_agg).
-        ``post_half``: those products as fp16 rows (bf16 mode, when their consumer is the bf16 edge update with resident weights:
-        the products are gathered once per incident edge, so their bytes dominate what the edge update reads).
+        ``post`` (inference): see ``Post`` - fills ``BlockOut.posts`` and, with ``post.zero``, ``BlockOut.next_agg``.
+        ``head`` (bf16 / fp32 inference, decoder) = (packed head MLP, residual operand or None): the node update and the output
+        head that follows it in one launch; ``BlockOut.x`` is then the HEAD'S OUTPUT instead of the new node rows.
         ``seg`` (bf16 inference, no residual, no e'): the plan's segment-aligned tiles (``GraphPlan.seg_tiles()``) - the edge update
         runs on the padded edge list (batch-shared per-edge operands must be in padded order, ``SegTiles.pad_rows``), writes the
         aggregate with plain stores as bf16 rows in the K order the node update's matrix product reads (a quarter of the bytes
         of the fp32 round trip; no zero fill when every destination has an edge).  ``seg`` with ``agg_acc`` (a processor block): the
         edge update adds its segment sums onto ``agg_acc`` in place - the previous block's aggregate (include/gw_amd.h:
         GW_EDGE_SEGMENT_TILES); edge tiles then cover the padded list, and no next aggregate is zero-filled."""
-        n_dst, n_edges = plan.n_dst, plan.num_edges
-        if _autograd_on(self, x_src.tensor, x_dst.tensor, e_in.tensor, e_res, x_node.tensor, x_res):
+        n_dst, n_edges, device = plan.n_dst, plan.num_edges, plan.src.device
+        e_res = FEED_ZERO if e_res is None else e_res
+        x_res = FEED_ZERO if x_res is None else x_res
+        if _autograd_on(self, x_src.tensor, x_dst.tensor, e_in.tensor, e_res.tensor, x_node.tensor, x_res.tensor):
             agg, e_out = ag.edge_update(self.edge_model.edge_mlp, plan, batch, (x_src.spec(), x_dst.spec(), e_in.spec()),
-                                        want_edges, x_src.tensor, x_dst.tensor, e_in.tensor, e_res, e_res_rows_pb)
-            x_new = ag.node_update(self.node_model.node_mlp, batch * n_dst, n_dst, x_node.spec(), x_node.tensor, x_res,
-                                   x_res_rows_pb, agg)
-            return x_new, e_out
+                                        want_edges, x_src.tensor, x_dst.tensor, e_in.tensor, e_res.tensor, e_res.rows_pb)
+            x_new = ag.node_update(self.node_model.node_mlp, batch * n_dst, n_dst, x_node.spec(), x_node.tensor, x_res.tensor,
+                                   x_res.rows_pb, agg)
+            return BlockOut(x_new, e_out)
         if seg is not None and agg_acc is not None:
             if want_edges not in (False, "tiles"):
                 raise RuntimeError("graph_weather_amd: a processor block on segment-aligned tiles hands e' over as edge tiles")
             agg = agg_acc
             n_edges = seg.n_pad  # (the tile buffers cover the padded list)
         elif seg is not None:
-            if want_edges or e_res is not None:
+            if want_edges or e_res.tensor is not None:
                 raise RuntimeError("graph_weather_amd: segment-aligned tiles come without residual and without e'")
             if seg.split:  # pieces of long runs meet in fp32 atomics
                 agg = agg_zeroed if agg_zeroed is not None else torch.zeros((batch * n_dst, 256), dtype=torch.float32, device=device)
@@ -412,30 +449,21 @@ class GraphNetBlock(nn.Module):
             e_out = torch.empty(ops.edge_tiles_bytes(batch, n_edges), dtype=torch.uint8, device=device)
         else:
             e_out = torch.empty((batch * n_edges, 256), dtype=torch.float32, device=device) if want_edges else None
-        res_op = ops.ZERO if e_res is None else Operand(e_res, e_res_rows_pb, 256, tiles=(e_res.dtype == torch.uint8))
         ops.edge_update_forward(self.edge_model.edge_mlp.packed(), batch, plan.src if seg is None else seg.src,
                                 plan.dst if seg is None else seg.dst, x_src.operand(), x_dst.operand(),
-                                e_in.operand(), res_op, n_dst, agg, e_out, tag=tag, deterministic=self.deterministic,
+                                e_in.operand(), e_res.operand(), n_dst, agg, e_out, tag=tag, deterministic=self.deterministic,
                                 segment_tiles=seg is not None, segment_split=seg is not None and seg.split and agg_acc is None)
-        res_x = ops.ZERO if x_res is None else Operand(x_res, x_res_rows_pb, 256)
+        pm_n, agg_op = self.node_model.node_mlp.packed(), Operand(agg, n_dst, 256)
         if head is not None:
-            # (bf16 inference, decoder) the node update and the output head that follows it in one launch: ``head`` = (packed
-            # head MLP, residual operand or None); returns the head's output instead of the new node rows
-            if x_res is not None:
+            if x_res.tensor is not None:
                 raise RuntimeError("graph_weather_amd: the fused node update + head has no node residual (decoder rows are zeros)")
-            y = ops.node_update_head_forward(self.node_model.node_mlp.packed(), head[0], batch * n_dst, n_dst, x_node.operand(),
-                                             Operand(agg, n_dst, 256), head[1])
-            return y, e_out
-        if post_w is not None:
-            next_agg = torch.empty((batch * n_dst, 256), dtype=torch.float32, device=device) if post_zero else None
-            if seg is not None and agg_acc is not None and not post_zero:
-                next_agg = None
-            x_new, posts = ops.node_update_forward(self.node_model.node_mlp.packed(), batch * n_dst, n_dst, x_node.operand(), res_x,
-                                                   Operand(agg, n_dst, 256), post_w=post_w, zero_rows=next_agg, post_half=post_half)
-            return x_new, e_out, posts, next_agg
-        x_new = ops.node_update_forward(self.node_model.node_mlp.packed(), batch * n_dst, n_dst, x_node.operand(), res_x,
-                                        Operand(agg, n_dst, 256))
-        return x_new, e_out
+            return BlockOut(ops.node_update_head_forward(pm_n, head[0], batch * n_dst, n_dst, x_node.operand(), agg_op, head[1]), e_out)
+        if post is not None:
+            next_agg = torch.empty((batch * n_dst, 256), dtype=torch.float32, device=device) if post.zero else None
+            x_new, posts = ops.node_update_forward(pm_n, batch * n_dst, n_dst, x_node.operand(), x_res.operand(), agg_op,
+                                                   post_w=post.w, zero_rows=next_agg, post_half=post.half)
+            return BlockOut(x_new, e_out, posts, next_agg)
+        return BlockOut(ops.node_update_forward(pm_n, batch * n_dst, n_dst, x_node.operand(), x_res.operand(), agg_op), e_out)
 
     def params_key(self) -> tuple:
         return _version_key(list(self.parameters()))
@@ -465,6 +493,78 @@ def _pad256(t: torch.Tensor) -> torch.Tensor:
     if t.shape[1] > 256:
         raise RuntimeError("graph_weather_amd: a %d-wide table reached the 256-wide kernels" % int(t.shape[1]))
     return t if t.shape[1] == 256 else torch.nn.functional.pad(t, (0, 256 - t.shape[1]))
+
+
+# ---- what the bipartite (encoder / decoder) stages of every model share: layers.py, analysis.py, regional.py --------------------
+
+
+def cached(module: nn.Module, name: str, params, make, token=None):
+    """A batch-independent tensor of ``module``'s inference path from its ``_cache``, remade when a parameter of ``params`` (or
+    ``token``, e.g. the coordinate set) changes.  Training: part of the graph, recomputed every step."""
+    if _autograd_on(module):
+        return make()
+    return module._cache.get(name, _version_key(params) if token is None else (_version_key(params), token), make)
+
+
+def plans_on(memo: dict, device, plans) -> tuple:
+    """``plans`` moved to ``device``, once per device (plans live outside state_dict, like encoder.graph / encoder.latent_graph,
+    encoder.py:107,109)."""
+    key = str(device)
+    if key not in memo:
+        memo[key] = tuple(p.to(device) for p in plans)
+    return memo[key]
+
+
+def bipartite_block_route(blk: GraphNetBlock, n_edges: int, is_wide: bool, autograd: bool) -> str:
+    """routes.block_route of an encoder's / decoder's bipartite block for one call."""
+    if is_wide or autograd:
+        return routes.BLOCK_ROWS
+    return routes.block_route(_form(blk.edge_model.edge_mlp), blk.node_model.node_mlp.compute_dtype, n_edges, False, False,
+                              bool(blk.deterministic))
+
+
+def edge_sum_product(blk: GraphNetBlock, plan: GraphPlan, e: torch.Tensor, half: bool = False) -> torch.Tensor:
+    """Wa . S with S[dst] = the sum of the batch-shared edge embedding e over the destination's edges: what stands in the node
+    update for the residual when the edge update adds none (sum(LN(.) + e) = sum(LN(.)) + S).  ``half``: as fp16 rows, like every
+    layer-1 product of the bf16 path (the node update adds them to its fp32 accumulator and rounds the sum to bf16)."""
+    pm_n = blk.node_model.node_mlp.packed()
+    e_sum = ag.segment_sum_rows(e, int(e.shape[0]), 1, 1, plan.n_dst, plan.dst_ptr(), None)
+    return ops.project_forward([pm_n.w1[1]], Operand(e_sum, plan.n_dst, 256), plan.n_dst, plan.n_dst, out_half=half)[0]
+
+
+def encoder_block_products(blk: GraphNetBlock, xm: torch.Tensor, e: torch.Tensor, train: bool, passthrough: bool = False):
+    """The batch-independent layer-1 products of an encoder block, whose destination rows xm are the same for every sample
+    (encoder.py:199-204): (Wd.xm of the edge MLP, We.e of the edge MLP, Wx.xm of the node MLP, e).  ``train``: differentiable;
+    with ``passthrough`` e then comes back as an output of the node that made We.e: it is also the block's residual, and the two
+    gradients of the [E, 256] table leave that node as one (autograd.ProjectFunction)."""
+    M, E = int(xm.shape[0]), int(e.shape[0])
+    mlp_e, mlp_n = blk.edge_model.edge_mlp, blk.node_model.node_mlp
+    if train:
+        pd_xm = ag.project(mlp_e, (1,), xm, M, M)[0]
+        pe = ag.project(mlp_e, (2,), e, E, E, passthrough=passthrough)
+        return pd_xm, pe[0], ag.project(mlp_n, (0,), xm, M, M)[0], pe[1] if passthrough else e
+    pm_e, pm_n = mlp_e.packed(), mlp_n.packed()
+    return (ops.project_forward([pm_e.w1[1]], Operand(xm, M, 256), M, M)[0], ops.project_forward([pm_e.w1[2]], Operand(e, E, 256), E, E)[0],
+            ops.project_forward([pm_n.w1[0]], Operand(xm, M, 256), M, M)[0], e)
+
+
+def decoder_block_products(blk: GraphNetBlock, x: torch.Tensor, batch: int, e: torch.Tensor, train: bool, cached_pe,
+                           passthrough: bool = False, half: bool = False, ps: Optional[torch.Tensor] = None):
+    """The layer-1 products of a decoder block, whose destination rows are zeros (assimilator_decoder.py:84,190-192): (Ws.x per
+    source row, We.e, e).  Layer 1 of the edge MLP is then relu(Ws.x[src] + (We.e + b)): a gather-add of a per-node product and a
+    batch-independent per-edge product - no matrix work per edge.  Inference: ``cached_pe(make)`` returns the caller's cached
+    We.e or makes it; ``ps``: Ws.x when the caller's previous launch made it; ``half``: Ws.x as fp16 rows.  ``train`` /
+    ``passthrough``: as in ``encoder_block_products``."""
+    mlp_e = blk.edge_model.edge_mlp
+    n, E = int(x.shape[0]) // batch, int(e.shape[0])
+    if train:
+        ps = ag.project(mlp_e, (0,), x.contiguous(), batch * n, n)[0]
+        pe = ag.project(mlp_e, (2,), e, E, E, passthrough=passthrough)
+        return ps, pe[0], pe[1] if passthrough else e
+    pm_e = mlp_e.packed()
+    if ps is None:
+        ps = ops.project_forward([pm_e.w1[0]], Operand(x.contiguous(), n, 256), batch * n, n, out_half=half)[0]
+    return ps, cached_pe(lambda: ops.project_forward([pm_e.w1[2]], Operand(e, E, 256), E, E)[0]), e
 
 
 class GraphProcessor(nn.Module):
@@ -569,30 +669,30 @@ class GraphProcessor(nn.Module):
         seg = plan.seg_tiles()
         return seg if routes.stack_on_segment_tiles(forms, plan.num_edges, None if seg is None else seg.max_slots) else None
 
-    def _shared_e0_seg(self, blk, e_cur: torch.Tensor, seg):
+    def _shared_e0_seg(self, blk, e_cur: torch.Tensor, seg) -> SharedE0:
         """(We . e in padded order, e as one shared set of bf16 edge tiles over the padded list) of batch-independent edge
         features on segment-aligned tiles, cached per (e, weights)."""
         key = (e_cur.data_ptr(), _ver(e_cur), blk.params_key(), seg.n_pad)
 
         def make():
-            pe = self._shared_e0(blk, e_cur, int(e_cur.shape[0]), tiles=False)[1]
-            return seg.pad_rows(pe), ops.edge_rows_to_tiles(seg.pad_rows(e_cur), 1, seg.n_pad, seg.n_pad)
+            pe = self._shared_e0(blk, e_cur, int(e_cur.shape[0]), tiles=False).pe
+            return SharedE0(seg.pad_rows(pe), ops.edge_rows_to_tiles(seg.pad_rows(e_cur), 1, seg.n_pad, seg.n_pad))
 
         return self._cache.get("e0_seg", key, make, hold=e_cur)
 
-    def _shared_e0(self, blk, e_cur: torch.Tensor, n_edges: int, tiles: bool = True):
-        """(key, We . e, e, [e as one shared set of bf16 edge tiles]) of batch-independent edge features, cached per (e, weights).
-        ``tiles=False``: the caller reads only the product (the segment-tile route keeps its own padded tile set)."""
+    def _shared_e0(self, blk, e_cur: torch.Tensor, n_edges: int, tiles: bool = True) -> SharedE0:
+        """(We . e, e as one shared set of bf16 edge tiles - where block 0 runs on the resident bf16 kernel, else None) of
+        batch-independent edge features, cached per (e, weights).  ``tiles=False``: the caller reads only the product (the
+        segment-tile route keeps its own padded tile set)."""
         mlp_e = blk.edge_model.edge_mlp
         pm_e = mlp_e.packed()
         key = (e_cur.data_ptr(), _ver(e_cur), blk.params_key())
         pe = self._cache.get("e0_pe", key, lambda: ops.project_forward([pm_e.w1[2]], Operand(e_cur, n_edges, 256), n_edges, n_edges)[0],
                              hold=e_cur)
-        out = (key, pe, e_cur)
-        if tiles and routes.resident_bf16(routes.MlpForm.of(mlp_e, pm_e), n_edges):
-            # the residual of the resident bf16 kernel: e as one shared tile set
-            out = out + (self._cache.get("e0_tiles", key, lambda: ops.edge_rows_to_tiles(e_cur, 1, n_edges, n_edges), hold=e_cur),)
-        return out
+        if not (tiles and routes.resident_bf16(routes.MlpForm.of(mlp_e, pm_e), n_edges)):
+            return SharedE0(pe, None)
+        # the residual of the resident bf16 kernel: e as one shared tile set
+        return SharedE0(pe, self._cache.get("e0_tiles", key, lambda: ops.edge_rows_to_tiles(e_cur, 1, n_edges, n_edges), hold=e_cur))
 
     def _run_blocks(self, lo: int, hi: int, x: torch.Tensor, e: torch.Tensor, e_shared: bool, plan: GraphPlan, batch: int,
                     want_edges: bool, pre_proj=None, tail_w=None, tail_half: bool = False):
@@ -638,9 +738,9 @@ class GraphProcessor(nn.Module):
                 if train:
                     pe = ag.project(mlp_e, (2,), e_cur, n_edges, n_edges)[0]
                 elif seg is not None:
-                    pe = self._shared_e0_seg(blk, e_cur, seg)[0]
+                    pe = self._shared_e0_seg(blk, e_cur, seg).pe
                 else:
-                    pe = self._shared_e0(blk, e_cur, n_edges)[1]
+                    pe = self._shared_e0(blk, e_cur, n_edges).pe
                 e_in = Feed(pe, 0, "proj")
             elif tiled:
                 if e_cur.dtype != torch.uint8:  # per-sample rows handed over by a caller: into the tile format once
@@ -653,13 +753,13 @@ class GraphProcessor(nn.Module):
             # shape: set_compute_dtype applied to a sub-module can leave neighbours in different modes)
             out_kind = routes.edge_out_kind(route, bool(need_e), route_of(i + 1) if not last else None)
             if seg is not None and shared:
-                e_res = self._shared_e0_seg(blk, e_cur, seg)[1]
+                e_res = self._shared_e0_seg(blk, e_cur, seg).tiles
             elif shared and tiled:
-                e_res = self._shared_e0(blk, e_cur, n_edges)[3]
+                e_res = self._shared_e0(blk, e_cur, n_edges).tiles
             else:
                 e_res = e_cur
             # what the node update of this block also produces (inference): the next block's layer-1 node products
-            post_w, post_zero, post_half = None, False, False
+            post = None
             if not train:
                 pm_n = blk.node_model.node_mlp.packed()
                 if i + 1 < len(self.blocks):
@@ -667,28 +767,28 @@ class GraphProcessor(nn.Module):
                     nxt = nxt_mlp.packed()
                     if nxt.weight_dtype == pm_n.weight_dtype and i + 1 < hi:
                         # (segment-aligned stack: the next block adds onto this block's aggregate - nothing to zero-fill)
-                        post_w, post_zero = [nxt.w1[0], nxt.w1[1]], seg is None
                         # block i + 1 >= 1 reads per-sample edge tiles, i.e. runs its layer 1 in the bf16 layer-1 kernel, which
                         # gathers these products once per edge: hand them over as fp16 rows
-                        post_half = routes.post_products_half(route_of(i + 1))
+                        post = Post([nxt.w1[0], nxt.w1[1]], zero=seg is None, half=routes.post_products_half(route_of(i + 1)))
                 elif tail_w is not None and all(w_.dtype == pm_n.w_out.dtype for w_ in tail_w):
-                    post_w = list(tail_w)
-                    post_half = bool(tail_half)
+                    post = Post(list(tail_w), half=bool(tail_half))
             if seg is not None and agg_buf is None:
                 agg_buf = torch.zeros((batch * n, 256), dtype=torch.float32, device=x.device)
-            res = blk.run(batch, plan, Feed(ps, n, "proj"), Feed(pd, n, "proj"), e_in, e_res, 0 if shared else n_edges,
-                          Feed(x, n, "raw"), x, n, out_kind, x.device, tag="processor_edge", agg_zeroed=agg_buf,
-                          post_w=post_w, post_zero=post_zero, post_half=post_half, seg=seg, agg_acc=agg_buf if seg is not None else None)
-            x, e_new = res[0], res[1]
-            if post_w is not None:
-                if post_zero:
-                    carried = (res[2][0], res[2][1], res[3])
+            x_rows = Feed(x, n, "raw")  # (layer-1 operand of the node MLP and its residual)
+            out = blk.run(batch, plan, x_src=Feed(ps, n, "proj"), x_dst=Feed(pd, n, "proj"), e_in=e_in, x_node=x_rows,
+                          e_res=Feed(e_res, 0 if shared else n_edges, "tiles" if e_res.dtype == torch.uint8 else "raw"), x_res=x_rows,
+                          want_edges=out_kind, tag="processor_edge", agg_zeroed=agg_buf, post=post, seg=seg,
+                          agg_acc=agg_buf if seg is not None else None)
+            x = out.x
+            if post is not None:
+                if post.zero:
+                    carried = (out.posts[0], out.posts[1], out.next_agg)
                 elif seg is not None and i + 1 < hi:
-                    carried = (res[2][0], res[2][1], agg_buf)  # the running aggregate goes on to the next block
+                    carried = (out.posts[0], out.posts[1], agg_buf)  # the running aggregate goes on to the next block
                 else:
-                    tail = res[2]
-            if e_new is not None:
-                e_cur, shared = e_new, False
+                    tail = out.posts
+            if out.e is not None:
+                e_cur, shared = out.e, False
         return x, e_cur, shared, tail
 
     def _plan_for(self, edge_index: torch.Tensor, num_nodes: int) -> GraphPlan:
@@ -752,30 +852,20 @@ class Encoder(nn.Module):
         self._dev_plans = {}
         self._cache = KeyedCache()
 
-    # plans live outside state_dict (like encoder.graph / encoder.latent_graph, encoder.py:107,109)
     def _plans(self, device):
-        key = str(device)
-        if key not in self._dev_plans:
-            self._dev_plans[key] = (self.graphs.enc_plan.to(device), self.graphs.lat_plan.to(device))
-        return self._dev_plans[key]
-
-    def _cached(self, name: str, params, fn):
-        if _autograd_on(self):  # training: batch-independent embeddings are part of the graph, recomputed every step
-            return fn()
-        return self._cache.get(name, _version_key(params), fn)
+        return plans_on(self._dev_plans, device, (self.graphs.enc_plan, self.graphs.lat_plan))
 
     def mesh_embedding(self) -> torch.Tensor:
         """node_encoder(h3_nodes): batch independent (encoder.py:199-205 recomputes it for every sample)."""
         ps = list(self.node_encoder.parameters()) + [self.h3_nodes]
-        return self._cached("mesh", ps, lambda: self.node_encoder.table(self.h3_nodes if _autograd_on(self) else self.h3_nodes.detach()))
+        return cached(self, "mesh", ps, lambda: self.node_encoder.table(self.h3_nodes if _autograd_on(self) else self.h3_nodes.detach()))
 
     def encoder_edge_embedding(self, plan: GraphPlan) -> torch.Tensor:
-        return self._cached("enc_e", list(self.edge_encoder.parameters()), lambda: self.edge_encoder.table(plan.edge_attr))
+        return cached(self, "enc_e", list(self.edge_encoder.parameters()), lambda: self.edge_encoder.table(plan.edge_attr))
 
     def latent_edge_embedding(self, plan: GraphPlan) -> torch.Tensor:
         """latent_edge_encoder(attr) once on [E_lat, 2] in dst-sorted order (encoder.py:235-241 repeats B times)."""
-        return self._cached("lat_e", list(self.latent_edge_encoder.parameters()),
-                            lambda: self.latent_edge_encoder.table(plan.edge_attr))
+        return cached(self, "lat_e", list(self.latent_edge_encoder.parameters()), lambda: self.latent_edge_encoder.table(plan.edge_attr))
 
     def encode(self, features: torch.Tensor, post_w=None):
         """encoder.py:199-223 -> mesh node features [(B*M), D] (batch-major, reversed-rank mesh order).  ``post_w`` (inference,
@@ -809,8 +899,10 @@ class Encoder(nn.Module):
         e = self.encoder_edge_embedding(enc_plan)
         blk = self.graph_processor.blocks[0]
         _check_native_dims(*self.graph_processor._dims)
-        pd_xm, pe, px_xm, e = self._static_projections(blk, xm, e)
-        x_src, e_res = Feed(xg, G, "raw"), e
+        # (cached per weight version; under autograd e comes back as an output of the node that made We.e)
+        pd_xm, pe, px_xm, e = cached(self, "enc_proj", list(self.parameters()),
+                                     lambda: encoder_block_products(blk, xm, e, _autograd_on(self), passthrough=True))
+        x_src, e_res = Feed(xg, G, "raw"), Feed(e, 0, "raw")
         seg = None
         if team or x3:
             # 16-bit inference (bf16: the team-pipelined edge kernel, csrc/gw_edge16t.hip; bf16x3: csrc/gw_split.hip): every operand
@@ -827,7 +919,7 @@ class Encoder(nn.Module):
         if team:
             seg = enc_plan.seg_tiles(split=True)  # (a polar mesh cell collects hundreds of grid nodes: runs split over tiles)
             if seg is not None:
-                pe = self._cached("enc_pe_pad", list(self.parameters()), lambda: seg.pad_rows(pe))
+                pe = cached(self, "enc_pe_pad", list(self.parameters()), lambda: seg.pad_rows(pe))
         if fused:
             # float32 inference: node encoder and edge update in ONE launch (csrc/gw_encoder_fused.hip; one edge per grid node, so
             # the row an edge reads is the row its column can make itself), without residual as on the 16-bit routes above: Wa.S
@@ -859,14 +951,10 @@ class Encoder(nn.Module):
                 x, posts = ops.node_update_forward(pm_n, n_rows, n_dst, x_op, res_x, agg_op, post_w=post_w, zero_rows=agg0)
                 return x, posts, agg0
             return ops.node_update_forward(pm_n, n_rows, n_dst, x_op, res_x, agg_op)
-        if post_w is not None:
-            x, _, posts, agg0 = blk.run(B, enc_plan, x_src, Feed(pd_xm, 0, "proj"), Feed(pe, 0, "proj"), e_res, 0,
-                                        Feed(px_xm, 0, "proj"), xm, 0, False, features.device, tag="encoder_edge",
-                                        post_w=post_w, post_zero=True, seg=seg)
-            return x, posts, agg0
-        x, _ = blk.run(B, enc_plan, x_src, Feed(pd_xm, 0, "proj"), Feed(pe, 0, "proj"), e_res, 0,
-                       Feed(px_xm, 0, "proj"), xm, 0, False, features.device, tag="encoder_edge", seg=seg)
-        return x
+        out = blk.run(B, enc_plan, x_src=x_src, x_dst=Feed(pd_xm, 0, "proj"), e_in=Feed(pe, 0, "proj"), x_node=Feed(px_xm, 0, "proj"),
+                      e_res=e_res, x_res=Feed(xm, 0, "raw"), tag="encoder_edge", seg=seg,
+                      post=None if post_w is None else Post(post_w, zero=True))
+        return out.x if post_w is None else (out.x, out.posts, out.next_agg)
 
     def fused_path(self, features: Optional[torch.Tensor] = None) -> bool:
         """float32 inference with the node encoder and the edge update in one launch (``routes.encoder_fused``).  Decided from the
@@ -877,14 +965,10 @@ class Encoder(nn.Module):
         if wide.encoder_is_wide(self) or ne.compute_dtype != torch.float32 or mlp_e.compute_dtype != torch.float32:
             return False
 
-        def form(m):
-            native = not m._layout()[4] and m._norm() is not None and len(m._linears()) == 3
-            return routes.MlpForm(torch.float32, 1 if native else -1, 0 if native else -1, native)
-
         # (the grad-mode-off first pass of a recomputed training segment counts as training: the two launches give the bits of
         # the replay the gradients come from; the fused launch sums in another order)
         train = _autograd_on(self, features) or ag.in_recomputed_first_pass()
-        return routes.encoder_fused(form(ne), ne.native_k(), form(mlp_e), mlp_n.compute_dtype, self.graphs.enc_plan.num_edges,
+        return routes.encoder_fused(native_fp32_form(ne), ne.native_k(), native_fp32_form(mlp_e), mlp_n.compute_dtype, self.graphs.enc_plan.num_edges,
                                     self.num_latlons, False, train, bool(blk.deterministic), bool(ops.ENCODER_FUSED))
 
     def team_path(self, features: Optional[torch.Tensor] = None) -> bool:
@@ -894,15 +978,9 @@ class Encoder(nn.Module):
         return self._block_route(features) == routes.BLOCK_TEAM
 
     def _block_route(self, features: Optional[torch.Tensor] = None) -> str:
-        """routes.block_route of the encoder's bipartite block for this call."""
-        blk = self.graph_processor.blocks[0]
-        mlp_e, mlp_n = blk.edge_model.edge_mlp, blk.node_model.node_mlp
         is_wide = wide.encoder_is_wide(self)
-        auto = False if is_wide else _autograd_on(self, features)
-        if is_wide or auto:
-            return routes.BLOCK_ROWS
-        return routes.block_route(_form(mlp_e), mlp_n.compute_dtype, self.graphs.enc_plan.num_edges, False, False,
-                                  bool(blk.deterministic))
+        return bipartite_block_route(self.graph_processor.blocks[0], self.graphs.enc_plan.num_edges, is_wide,
+                                     not is_wide and _autograd_on(self, features))
 
     def split_path(self, features: Optional[torch.Tensor] = None) -> bool:
         """Inference with bf16x3 (split-operand) products in both MLPs of the encoder block: the edge update then runs with every
@@ -912,38 +990,7 @@ class Encoder(nn.Module):
     def _team_node_product(self, blk, plan: GraphPlan, e: torch.Tensor, px_xm: torch.Tensor) -> torch.Tensor:
         """Wx.xm + Wa.S with S[dst] = the sum of the (batch-independent) edge features e over the destination's edges: the
         node-update layer-1 operand of the mesh rows when the edge kernel adds no residual.  Cached per weight version."""
-        def make():
-            pm_n = blk.node_model.node_mlp.packed()
-            n_e = int(e.shape[0])
-            e_sum = ag.segment_sum_rows(e, n_e, 1, 1, plan.n_dst, plan.dst_ptr(), None)
-            pa = ops.project_forward([pm_n.w1[1]], Operand(e_sum, plan.n_dst, 256), plan.n_dst, plan.n_dst)[0]
-            return wide.add_rows(px_xm, pa)
-
-        return self._cached("enc_proj_team", list(self.parameters()), make)
-
-    def _static_projections(self, blk, xm: torch.Tensor, e: torch.Tensor):
-        """Batch-independent layer-1 products of the encoder block (mesh rows are the same for every sample,
-        encoder.py:199-204): Wd.xm (edge MLP), We.e (edge MLP), Wx.xm (node MLP) - cached per weight version; and e itself (under
-        autograd: as an output of the node that made We.e)."""
-        ps = list(self.parameters())
-
-        def make():
-            M, G = int(xm.shape[0]), int(e.shape[0])
-            if _autograd_on(self):
-                pd_xm = ag.project(blk.edge_model.edge_mlp, (1,), xm, M, M)[0]
-                # (e comes back as an output of the same autograd node: it is also the block's residual, and the two gradients of
-                # the [E, 256] table then leave that node as one - autograd.ProjectFunction)
-                pe, e_same = ag.project(blk.edge_model.edge_mlp, (2,), e, G, G, passthrough=True)
-                px_xm = ag.project(blk.node_model.node_mlp, (0,), xm, M, M)[0]
-                return pd_xm, pe, px_xm, e_same
-            pm_e = blk.edge_model.edge_mlp.packed()
-            pm_n = blk.node_model.node_mlp.packed()
-            pd_xm = ops.project_forward([pm_e.w1[1]], Operand(xm, M, 256), M, M)[0]
-            pe = ops.project_forward([pm_e.w1[2]], Operand(e, G, 256), G, G)[0]
-            px_xm = ops.project_forward([pm_n.w1[0]], Operand(xm, M, 256), M, M)[0]
-            return pd_xm, pe, px_xm, e
-
-        return self._cached("enc_proj", ps, make)
+        return cached(self, "enc_proj_team", list(self.parameters()), lambda: wide.add_rows(px_xm, edge_sum_product(blk, plan, e)))
 
     def forward(self, features: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """encoder.py:153-242.  Returns reference-order tensors: replicated graph by default, the single shared
@@ -1052,15 +1099,10 @@ class AssimilatorDecoder(nn.Module):
         self._cache = KeyedCache()
 
     def _plan(self, device) -> GraphPlan:
-        key = str(device)
-        if key not in self._dev_plans:
-            self._dev_plans[key] = self.graphs.dec_plan.to(device)
-        return self._dev_plans[key]
+        return plans_on(self._dev_plans, device, (self.graphs.dec_plan,))[0]
 
     def edge_embedding(self, plan: GraphPlan) -> torch.Tensor:
-        if _autograd_on(self):
-            return self.edge_encoder.table(plan.edge_attr)
-        return self._cache.get("dec_e", _version_key(list(self.edge_encoder.parameters())), lambda: self.edge_encoder.table(plan.edge_attr))
+        return cached(self, "dec_e", list(self.edge_encoder.parameters()), lambda: self.edge_encoder.table(plan.edge_attr))
 
     def prefetch_tables(self, dev) -> Optional["torch.cuda.Stream"]:
         """Cold forward (weights changed since the tables were made), inference, fp32 / bf16x3: the decoder's two big batch-
@@ -1106,15 +1148,9 @@ class AssimilatorDecoder(nn.Module):
         return self._block_route() == routes.BLOCK_TEAM
 
     def _block_route(self) -> str:
-        """routes.block_route of the decoder's bipartite block."""
-        blk = self.graph_processor.blocks[0]
-        mlp_e, mlp_n = blk.edge_model.edge_mlp, blk.node_model.node_mlp
         is_wide = wide.decoder_is_wide(self)
-        auto = False if is_wide else _autograd_on(self)
-        if is_wide or auto:
-            return routes.BLOCK_ROWS
-        return routes.block_route(_form(mlp_e), mlp_n.compute_dtype, self.graphs.dec_plan.num_edges, False, False,
-                                  bool(blk.deterministic))
+        return bipartite_block_route(self.graph_processor.blocks[0], self.graphs.dec_plan.num_edges, is_wide,
+                                     not is_wide and _autograd_on(self))
 
     def stream_path(self) -> bool:
         """float32 inference on the decoder-form edge kernel without residual (``routes.decoder_stream``).  Decided from the
@@ -1124,24 +1160,13 @@ class AssimilatorDecoder(nn.Module):
         mlp_e, mlp_n = blk.edge_model.edge_mlp, blk.node_model.node_mlp
         if mlp_e.compute_dtype != torch.float32 or wide.decoder_is_wide(self):
             return False
-        native = not mlp_e._layout()[4] and mlp_e._norm() is not None and len(mlp_e._linears()) == 3
-        form = routes.MlpForm(torch.float32, 1 if native else -1, 0 if native else -1, native)
-        return routes.decoder_stream(form, mlp_n.compute_dtype, self.graphs.dec_plan.num_edges, False, _autograd_on(self),
-                                     bool(blk.deterministic), bool(ops.EDGE_STREAM))
+        return routes.decoder_stream(native_fp32_form(mlp_e), mlp_n.compute_dtype, self.graphs.dec_plan.num_edges, False,
+                                     _autograd_on(self), bool(blk.deterministic), bool(ops.EDGE_STREAM))
 
     def _e_sum_product(self, plan: GraphPlan, e_rows: torch.Tensor, key, half: bool) -> torch.Tensor:
-        """Wa . S, S[dst] = sum of the (batch-shared) edge embedding over the destination's edges: the cached, batch-shared
-        projected operand that stands in the node update for the residual the edge update no longer adds (see ``decode``)."""
-        pm_n = self.graph_processor.blocks[0].node_model.node_mlp.packed()
-        n_e = plan.num_edges
-
-        def make_e_sum():
-            e_sum = ag.segment_sum_rows(e_rows, n_e, 1, 1, plan.n_dst, plan.dst_ptr(), None)
-            # (bf16 mode: fp16 rows, like every layer-1 product of that path: the node update adds them to its fp32
-            # accumulator and rounds the sum to bf16; fp32 / bf16x3: fp32 rows)
-            return ops.project_forward([pm_n.w1[1]], Operand(e_sum, plan.n_dst, 256), plan.n_dst, plan.n_dst, out_half=half)[0]
-
-        return self._cache.get("dec_e_sum", key, make_e_sum)
+        """The cached ``edge_sum_product`` of the decoder block: the batch-shared projected operand that stands in the node update
+        for the residual the edge update no longer adds (see ``decode``).  bf16 mode (``half``): fp16 rows; fp32 / bf16x3: fp32."""
+        return self._cache.get("dec_e_sum", key, lambda: edge_sum_product(self.graph_processor.blocks[0], plan, e_rows, half))
 
     def split_path(self) -> bool:
         """Inference with bf16x3 (split-operand) products in both MLPs of the decoder block (see ``Encoder.split_path``)."""
@@ -1163,29 +1188,23 @@ class AssimilatorDecoder(nn.Module):
         blk = self.graph_processor.blocks[0]
         _check_native_dims(*self.graph_processor._dims)
         # lat/lon rows are zeros (assimilator_decoder.py:84,190-192): x_dst = 0, node input [0 | agg], residual 0.
-        # Layer 1 of the edge MLP is then relu(Ws.x[src] + (We.e + b)): a gather-add of a per-mesh-node product and a
-        # cached batch-independent per-edge product - no matrix work per edge in layer 1.
         train = _autograd_on(self, processor_features)
         mlp_e = blk.edge_model.edge_mlp
         n_e = plan.num_edges
-        if train:
-            ps = ag.project(mlp_e, (0,), processor_features.contiguous(), B * M, M)[0]
-            pe, e = ag.project(mlp_e, (2,), e, n_e, n_e, passthrough=True)  # (e is the block's residual too: see Encoder._static_projections)
-        else:
-            pm_e = mlp_e.packed()
-            team = self.team_path()
-            if ps is None:
-                ps = ops.project_forward([pm_e.w1[0]], Operand(processor_features.contiguous(), M, 256), B * M, M, out_half=team)[0]
-            elif ps.dtype == torch.float16 and not team:
-                raise RuntimeError("graph_weather_amd: fp16 layer-1 products were handed to a decoder that cannot take them")
-            key = _version_key(list(self.edge_encoder.parameters()) + list(blk.parameters()))
-            e_rows = e
-            pe = self._cache.get("dec_pe", key, lambda: ops.project_forward([pm_e.w1[2]], Operand(e_rows, n_e, 256), n_e, n_e)[0])
+        team = not train and self.team_path()
+        if not train and ps is not None and ps.dtype == torch.float16 and not team:
+            raise RuntimeError("graph_weather_amd: fp16 layer-1 products were handed to a decoder that cannot take them")
+        key = None if train else _version_key(list(self.edge_encoder.parameters()) + list(blk.parameters()))
+        e_rows = e
+        # (under autograd e comes back as an output of the node that made We.e: it is the block's residual too)
+        ps, pe, e = decoder_block_products(blk, processor_features, B, e, train, lambda make: self._cache.get("dec_pe", key, make),
+                                           passthrough=True, half=team, ps=ps)
+        x_node, seg = FEED_ZERO, None
+        if not train:
             seg = plan.seg_tiles() if team else None
             if seg is not None:  # the per-edge product in the padded order of the segment-aligned tiles
                 pe_rows = pe
                 pe = self._cache.get("dec_pe_pad", key, lambda: seg.pad_rows(pe_rows))
-            x_node = FEED_ZERO
             x3 = self.split_path()
             stream = self.stream_path()
             if x3 or stream or routes.resident_bf16(_form(mlp_e), n_e):
@@ -1218,20 +1237,14 @@ class AssimilatorDecoder(nn.Module):
                 if (pm_h.hidden == 128 and pm_h.n_mid == 1 and pm_h.n_out <= 80 and pm_h.gamma is None and pm_nn.n_mid == 1
                         and pm_nn.gamma is not None and pm_nn.ln_width == 0):
                     head = (pm_h, res)
-        if not train and x_node is not FEED_ZERO:
-            out, _ = blk.run(B, plan, Feed(ps, M, "proj"), FEED_ZERO, Feed(pe, 0, "proj"), None, 0, x_node, None, 0, False, dev,
-                             tag="decoder_edge", head=head, seg=seg)
-            if head is not None:
-                return out.reshape(B, G, self.output_dim)
-            xg = out
-        elif head is not None and mlp_e.compute_dtype == torch.float32:
-            out, _ = blk.run(B, plan, Feed(ps, M, "proj"), FEED_ZERO, Feed(pe, 0, "proj"), e, 0, FEED_ZERO, None, 0, False, dev,
-                             tag="decoder_edge", head=head)
-            return out.reshape(B, G, self.output_dim)
-        else:
-            xg, _ = blk.run(B, plan, Feed(ps, M, "proj"), FEED_ZERO, Feed(pe, 0, "proj"), e, 0, FEED_ZERO, None, 0, False, dev,
-                            tag="decoder_edge")
-        y = self.node_decoder.run(xg, B * G, G, residual=res)
+        if x_node is FEED_ZERO and mlp_e.compute_dtype != torch.float32:
+            head = None  # (with the residual in the edge update, only the fp32 kernels take the node update + head launch)
+        e_res = None if e is None else Feed(e, 0, "tiles" if e.dtype == torch.uint8 else "raw")
+        out = blk.run(B, plan, x_src=Feed(ps, M, "proj"), x_dst=FEED_ZERO, e_in=Feed(pe, 0, "proj"), x_node=x_node, e_res=e_res,
+                      tag="decoder_edge", head=head, seg=seg)
+        if head is not None:
+            return out.x.reshape(B, G, self.output_dim)
+        y = self.node_decoder.run(out.x, B * G, G, residual=res)
         if y.shape[1] != self.output_dim:
             y = y[:, :self.output_dim]
         return y.reshape(B, G, self.output_dim)

@@ -25,9 +25,9 @@ from torch import nn
 
 from . import autograd as ag
 from . import mesh as _mesh
-from . import ops
 from .graphs import GraphPlan, _sincos, plan_from_coo
-from .layers import FEED_ZERO, Feed, GraphProcessor, KeyedCache, MLP, Processor, _autograd_on, _check_native_dims, _version_key
+from .layers import (FEED_ZERO, Feed, GraphProcessor, KeyedCache, MLP, Processor, _autograd_on, _check_native_dims, cached,
+                     decoder_block_products, encoder_block_products)
 from .ops import Operand
 from .utils import validate_lat_lons
 
@@ -322,12 +322,6 @@ class RegionalForecaster(nn.Module):
         self.node_decoder = MLP(c.node_dim, output_dim, c.hidden_dim_decoder, c.hidden_layers_decoder, **mk)
         self._cache = KeyedCache()
 
-    def _cached(self, name: str, params, token, fn):
-        """Batch-independent tensors of the inference path: recomputed when a parameter or the coordinate set changes."""
-        if _autograd_on(self):
-            return fn()
-        return self._cache.get(name, (_version_key(params), token), fn)
-
     def _is_wide(self) -> bool:
         from . import wide
 
@@ -381,44 +375,28 @@ class RegionalForecaster(nn.Module):
         # ---- encode: coordinates + regional cells through the bipartite block (:258, :266-269) ----
         xo = self.node_encoder.run(feats, B * N, N)
         enc_params = list(self.node_encoder.parameters()) + [self.h3_embeddings]
-        xm = self._cached("cells", enc_params, token,
-                          lambda: self.node_encoder.table(self.h3_embeddings[rows] if train else self.h3_embeddings.detach()[rows]))
-        e_enc = self._cached("enc_e", list(self.edge_encoder.parameters()), token, lambda: self.edge_encoder.table(enc_plan.edge_attr))
+        xm = cached(self, "cells", enc_params,
+                    lambda: self.node_encoder.table(self.h3_embeddings[rows] if train else self.h3_embeddings.detach()[rows]), token)
+        e_enc = cached(self, "enc_e", list(self.edge_encoder.parameters()), lambda: self.edge_encoder.table(enc_plan.edge_attr), token)
         blk = self.encoder_gnn.blocks[0]
-
-        def enc_projections():
-            if train:
-                return (ag.project(blk.edge_model.edge_mlp, (1,), xm, C, C)[0], ag.project(blk.edge_model.edge_mlp, (2,), e_enc, N, N)[0],
-                        ag.project(blk.node_model.node_mlp, (0,), xm, C, C)[0])
-            pm_e, pm_n = blk.edge_model.edge_mlp.packed(), blk.node_model.node_mlp.packed()
-            return (ops.project_forward([pm_e.w1[1]], Operand(xm, C, 256), C, C)[0],
-                    ops.project_forward([pm_e.w1[2]], Operand(e_enc, N, 256), N, N)[0],
-                    ops.project_forward([pm_n.w1[0]], Operand(xm, C, 256), C, C)[0])
-
-        pd_xm, pe, px_xm = self._cached("enc_proj", enc_params + list(self.edge_encoder.parameters()) + list(blk.parameters()),
-                                        token, enc_projections)
-        x, _ = blk.run(B, enc_plan, Feed(xo, N, "raw"), Feed(pd_xm, 0, "proj"), Feed(pe, 0, "proj"), e_enc, 0,
-                       Feed(px_xm, 0, "proj"), xm, 0, False, dev, tag="regional_encoder_edge")
+        pd_xm, pe, px_xm, _ = cached(self, "enc_proj", enc_params + list(self.edge_encoder.parameters()) + list(blk.parameters()),
+                                     lambda: encoder_block_products(blk, xm, e_enc, train), token)
+        x = blk.run(B, enc_plan, x_src=Feed(xo, N, "raw"), x_dst=Feed(pd_xm, 0, "proj"), e_in=Feed(pe, 0, "proj"),
+                    x_node=Feed(px_xm, 0, "proj"), e_res=Feed(e_enc, 0, "raw"), x_res=Feed(xm, 0, "raw"), tag="regional_encoder_edge").x
 
         # ---- process: message passing between the regional cells (:259, :272) ----
-        e_lat = self._cached("lat_e", list(self.latent_edge_encoder.parameters()), token,
-                             lambda: self.latent_edge_encoder.table(lat_plan.edge_attr))
+        e_lat = cached(self, "lat_e", list(self.latent_edge_encoder.parameters()),
+                       lambda: self.latent_edge_encoder.table(lat_plan.edge_attr), token)
         x, _ = self.processor.graph_processor.run_plan(x, lat_plan, e_lat, True, B, False)
 
         # ---- decode: reversed encoder edges into zero placeholders (:262, :275-279), head, residual (:284) ----
-        e_dec = self._cached("dec_e", list(self.decoder_edge_encoder.parameters()), token,
-                             lambda: self.decoder_edge_encoder.table(dec_plan.edge_attr))
+        e_dec = cached(self, "dec_e", list(self.decoder_edge_encoder.parameters()),
+                       lambda: self.decoder_edge_encoder.table(dec_plan.edge_attr), token)
         dblk = self.decoder_gnn.blocks[0]
-        mlp_e = dblk.edge_model.edge_mlp
-        if train:
-            ps = ag.project(mlp_e, (0,), x.contiguous(), B * C, C)[0]
-            pe_d = ag.project(mlp_e, (2,), e_dec, N, N)[0]
-        else:
-            ps = ops.project_forward([mlp_e.packed().w1[0]], Operand(x.contiguous(), C, 256), B * C, C)[0]
-            pe_d = self._cached("dec_pe", list(self.decoder_edge_encoder.parameters()) + list(dblk.parameters()), token,
-                                lambda: ops.project_forward([mlp_e.packed().w1[2]], Operand(e_dec, N, 256), N, N)[0])
-        xg, _ = dblk.run(B, dec_plan, Feed(ps, C, "proj"), FEED_ZERO, Feed(pe_d, 0, "proj"), e_dec, 0, FEED_ZERO, None, 0, False, dev,
-                         tag="regional_decoder_edge")
+        dec_params = list(self.decoder_edge_encoder.parameters()) + list(dblk.parameters())
+        ps, pe_d, _ = decoder_block_products(dblk, x, B, e_dec, train, lambda make: cached(self, "dec_pe", dec_params, make, token))
+        xg = dblk.run(B, dec_plan, x_src=Feed(ps, C, "proj"), x_dst=FEED_ZERO, e_in=Feed(pe_d, 0, "proj"), x_node=FEED_ZERO,
+                      e_res=Feed(e_dec, 0, "raw"), tag="regional_decoder_edge").x
         res = Operand(feats, N, self.output_dim)
         y = self.node_decoder.run(xg, B * N, N, residual=res)
         out = y.reshape(B, N, self.output_dim)

@@ -107,3 +107,30 @@ def test_bench_reads_the_per_kernel_pmc_summaries_of_the_round():
     assert bench.pmc_kernel_traffic("c2", ("no_such_kernel<",), grid) == (None, None, None)
     total, d, name = bench.pmc_traffic("c2")
     assert total is not None and name.startswith("r") and 0.5 <= d.get("mfma_busy_frac", 0.0) <= 1.0
+
+
+def test_native_fp32_form_equals_the_three_expressions_it_replaces():
+    """``layers.native_fp32_form`` against what ``set_deterministic``, ``Encoder.fused_path`` and
+    ``AssimilatorDecoder.stream_path`` each spelled out before, on edge MLPs of a block (three layer-1 slices, table output)."""
+    from graph_weather_amd.layers import EdgeProcessor, native_fp32_form
+
+    shapes = {  # (node / edge width, hidden width, hidden layers, norm)
+        "256 / LayerNorm / 2 hidden layers": (256, 256, 2, "LayerNorm"),
+        "128-wide": (128, 128, 2, "LayerNorm"),
+        "no norm": (256, 256, 2, None),
+        "3 hidden layers": (256, 256, 3, "LayerNorm"),
+        "1 hidden layer": (256, 256, 1, "LayerNorm"),
+    }
+    native_shapes = []
+    for name, (dim, hidden, layers, norm) in shapes.items():
+        m = EdgeProcessor(dim, dim, hidden, layers, norm).edge_mlp
+        got = native_fp32_form(m)
+        # Encoder.fused_path (its ``form(m)``) and AssimilatorDecoder.stream_path (``native`` / ``form``)
+        native = not m._layout()[4] and m._norm() is not None and len(m._linears()) == 3
+        assert got == MlpForm(torch.float32, 1 if native else -1, 0 if native else -1, native), name
+        # set_deterministic: the shapes it refused for float32
+        refused = m._layout()[4] or m._norm() is None or len(m._linears()) != 3
+        assert (not got.has_norm) == bool(refused), name
+        if native:
+            native_shapes.append(name)
+    assert native_shapes == ["256 / LayerNorm / 2 hidden layers"]
