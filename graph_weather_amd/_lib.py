@@ -60,6 +60,7 @@ EXPORTS = [
     "gw_cond_layernorm_fanout_forward", "gw_cond_layernorm_fanout_workspace_bytes", "gw_cond_layernorm_fanout_backward",
     "gw_linear_gather_grouped_forward", "gw_segment_sum_rows_grouped",
     "gw_ensemble_crps_workspace_bytes", "gw_ensemble_crps_forward", "gw_ensemble_crps_backward",
+    "gw_genda_input_forward", "gw_genda_input_backward", "gw_genda_guided_output_forward", "gw_genda_guided_output_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -503,6 +504,15 @@ def lib():
     L.gw_ensemble_crps_forward.argtypes = [c_int32] * 5 + [ctypes.c_double, c_int32] + [c_void_p] * 5 + [c_size_t, c_void_p, c_void_p]
     L.gw_ensemble_crps_backward.restype = c_int
     L.gw_ensemble_crps_backward.argtypes = [c_int32] * 5 + [ctypes.c_double, c_int32] + [c_void_p] * 7
+    L.gw_genda_input_forward.restype = c_int
+    L.gw_genda_input_forward.argtypes = [c_int32, c_int64] + [c_int32] * 5 + [c_float, c_void_p] + [c_void_p, c_int32] * 6 + [
+        c_void_p, c_void_p]
+    L.gw_genda_input_backward.restype = c_int
+    L.gw_genda_input_backward.argtypes = [c_int32, c_int64] + [c_int32] * 5 + [c_float, c_void_p] + [c_void_p, c_int32] * 5 + [c_void_p]
+    L.gw_genda_guided_output_forward.restype = c_int
+    L.gw_genda_guided_output_forward.argtypes = [c_int32, c_int64, c_int32, c_float, c_float, c_void_p] + [c_void_p, c_int32] * 3 + [c_void_p]
+    L.gw_genda_guided_output_backward.restype = c_int
+    L.gw_genda_guided_output_backward.argtypes = [c_int32, c_int64, c_int32, c_float, c_float, c_void_p] + [c_void_p, c_int32] * 3 + [c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

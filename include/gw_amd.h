@@ -1006,6 +1006,34 @@ int gw_ensemble_crps_backward(int32_t batch, int32_t members, int32_t nlon, int3
                               const float* pred, const float* target, const float* area_weights, const float* features_weights,
                               const float* dout, float* dpred, void* stream);
 
+/* GenDA (genda/model.py of the reference): the Denoiser's preconditioning with up to two conditioning columns (sensor mask, sensor
+ * values) and `copies` (1 or 2) evaluations in one pass; coefficients as for gw_gencast_precond_* above.  Source row r = b grid_rows
+ * + g of `batch` samples; c0, c1: one float per source row with a row stride each, either may be NULL (n_cond = the pointers given,
+ * in order).  input_forward writes (c_in(sigma_b) z[r] | x[r] | c0[r] | c1[r] | stat[g]) of widths w_z, w_x, n_cond, w_s to out row
+ * r and, with copies = 2, the same with ZERO conditioning to row batch grid_rows + r (the unconditional evaluation of classifier-free
+ * guidance: sample batch + b of a pass at batch 2 batch); drop = 1 writes zeros for the conditioning of copy 0 as well (the training
+ * dropout, decided on the host) and reads no conditioning.  c_noise [copies batch] (may be NULL).  With copies 1 and no
+ * conditioning the result is that of gw_gencast_precond_input_forward bit for bit.
+ * input_backward, dout [copies batch grid_rows, >= w_z + w_x + n_cond]: dz = c_in (dout_copy0 + dout_copy1), dx = dout_copy0 +
+ * dout_copy1 (copy order), dc0 / dc1 = columns w_z + w_x / + 1 of copy 0 (zeros with drop); each output may be NULL, not all.
+ * guided_output_forward, preds [2 batch grid_rows, width]: o_c = c_skip z + c_out preds[r], o_u = c_skip z + c_out preds[batch
+ * grid_rows + r], out = o_u + gamma (o_c - o_u), float32 in this order.  guided_output_backward: dz = c_skip dout, dpreds[r] =
+ * c_out gamma dout, dpreds[batch grid_rows + r] = c_out (1 - gamma) dout (dz or dpreds may be NULL).  batch grid_rows < 2^32.
+ * Plain stores, no atomics, no host reads. */
+int gw_genda_input_forward(int32_t batch, int64_t grid_rows, int32_t copies, int32_t drop, int32_t w_z, int32_t w_x, int32_t w_s,
+                           float sigma_data, const float* sigma, const float* z, int32_t ld_z, const float* x, int32_t ld_x, const float* c0,
+                           int32_t ld_c0, const float* c1, int32_t ld_c1, const float* stat, int32_t ld_stat, float* out, int32_t ld_out,
+                           float* c_noise, void* stream);
+int gw_genda_input_backward(int32_t batch, int64_t grid_rows, int32_t copies, int32_t drop, int32_t w_z, int32_t w_x, int32_t n_cond,
+                            float sigma_data, const float* sigma, const float* dout, int32_t ld_dout, float* dz, int32_t ld_dz, float* dx,
+                            int32_t ld_dx, float* dc0, int32_t ld_dc0, float* dc1, int32_t ld_dc1, void* stream);
+int gw_genda_guided_output_forward(int32_t batch, int64_t grid_rows, int32_t width, float sigma_data, float gamma, const float* sigma,
+                                   const float* z, int32_t ld_z, const float* preds, int32_t ld_preds, float* out, int32_t ld_out,
+                                   void* stream);
+int gw_genda_guided_output_backward(int32_t batch, int64_t grid_rows, int32_t width, float sigma_data, float gamma, const float* sigma,
+                                    const float* dout, int32_t ld_dout, float* dz, int32_t ld_dz, float* dpreds, int32_t ld_dpreds,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
