@@ -55,6 +55,7 @@ from .aurora import (  # noqa: F401  (csrc/gw_aurora.hip, csrc/gw_conv3d.hip, ma
 )
 from . import gencast  # noqa: F401  (csrc/gw_gencast.hip; its Encoder / Processor / Decoder / MLP stay in the module: the names above are the forecaster's)
 from . import gencast_graphs, gencast_model  # noqa: F401  (GenCast's GraphBuilder and Denoiser: batch-shared route of csrc/gw_gencast.hip)
+from . import gencast_sparse  # noqa: F401  (GenCast's sparse processor blocks: the masked attention of csrc/gw_sparse_attn.hip)
 from . import gencast_sampler  # noqa: F401  (GenCast's Sampler and WeightedMSELoss; the inverse transform of csrc/gw_sht.hip draws the noise)
 from .gencast_sampler import Sampler, WeightedMSELoss  # noqa: F401
 from .graphed import ForwardGraph  # noqa: F401  (the inference forward as one HIP graph)

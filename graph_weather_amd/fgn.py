@@ -25,7 +25,11 @@ and measurement.
 One deliberate deviation: the reference returns ``torch.stack(predictions, 1) if len(prediction) > 1 else
 predictions[0].unsqueeze(1)`` and ``len(prediction)`` is the batch size, so at B = 1 it drops every member but the first.  Here
 all members are returned at every B, as the reference's docstring promises.  Not reproduced: the reference's per-stage
-``assert not torch.isnan(...)`` host reads.  fp32 only, no dropout; ``sparse=True`` is not provided; there is no CPU path.
+``assert not torch.isnan(...)`` host reads.  fp32 only, no dropout; there is no CPU path.
+
+``sparse="native"`` (with ``use_edges_features=False``) runs the processor on ``gencast_sparse.SparseTransformer`` blocks.  Their
+first norm already sees the noise, so the mesh rows fan out to the B N copies before block 0 and every block runs at batch B N;
+``sparse=True`` asks for the reference's DGL backend and raises as the reference does without DGL.
 """
 from __future__ import annotations
 
@@ -41,7 +45,7 @@ from torch.autograd import Function
 from . import _lib
 from .aurora import _RowScale, _workspace
 from .gencast import (_ACT_CODE, MLP, CondTransformerBlock, Decoder, Encoder, _act_name, _Linear, _rows_in, _SegmentSumShared,
-                      edge_plan, gemm_tn_ordered)
+                      _sparse_blocks, _sparse_mode, edge_plan, gemm_tn_ordered)
 from .gencast_graphs import GraphBuilder
 from .gencast_model import Denoiser
 from .ops import on_device_of
@@ -221,12 +225,13 @@ class _LinearGatherGrouped(Function):
 # ---------------------------------------------------------------------------------------------------------------------
 class Processor(nn.Module):
     """FGN's processor (fgn/layers/processor.py): GenCast's transformer blocks over the mesh, conditioned on a noise vector
-    instead of an embedded noise level (there is no ``fourier_embedder``).  ``sparse=True`` (the reference's DGL backend) is not
-    provided."""
+    instead of an embedded noise level (there is no ``fourier_embedder``).  ``sparse="native"`` builds ``num_blocks``
+    ``gencast_sparse.SparseTransformer`` blocks, as ``gencast.Processor`` does; ``sparse=True`` (the reference's DGL backend) raises
+    as the reference does without DGL."""
 
     def __init__(self, latent_dim: int, hidden_dims: list, num_blocks: int, num_heads: int, noise_emb_dim: int,
                  edges_dim: Optional[int] = None, activation_layer: nn.Module = nn.ReLU, use_layer_norm: bool = True,
-                 sparse: bool = False):
+                 sparse=False):
         super().__init__()
         self.latent_dim = latent_dim
         if latent_dim % num_heads != 0:
@@ -236,8 +241,10 @@ class Processor(nn.Module):
             self.edges_mlp = MLP(input_dim=edges_dim, hidden_dims=hidden_dims, activation_layer=activation_layer,
                                  use_layer_norm=use_layer_norm, bias=True, activate_final=False)
         self.cond_transformers = nn.ModuleList()
-        if sparse:
-            raise ValueError("Please install DGL to use sparsity.")
+        self.sparse = _sparse_mode(sparse)
+        if self.sparse:
+            _sparse_blocks(self.cond_transformers, num_blocks, noise_emb_dim, latent_dim, num_heads, activation_layer)
+            return
         e_dim = hidden_dims[-1] if (edges_dim is not None) else None
         for _ in range(num_blocks - 1):  # concatenating multi-head attention
             self.cond_transformers.append(CondTransformerBlock(conditioning_dim=noise_emb_dim, input_dim=latent_dim,
@@ -285,7 +292,10 @@ class Processor(nn.Module):
         per node), one copy's ``edge_index`` and edge attributes."""
         edges_emb = self._edges(input_edge_attr)
         for cond_transformer in self.cond_transformers:
-            latent_mesh_nodes = cond_transformer._forward_shared(latent_mesh_nodes, edge_index, edges_emb, noise_vector, batch)
+            if self.sparse:
+                latent_mesh_nodes = cond_transformer._forward_shared(latent_mesh_nodes, edge_index, noise_vector, batch)
+            else:
+                latent_mesh_nodes = cond_transformer._forward_shared(latent_mesh_nodes, edge_index, edges_emb, noise_vector, batch)
         return latent_mesh_nodes
 
     def _forward_ensemble(self, latent_mesh_nodes: torch.Tensor, edge_index: torch.Tensor, noise_vector: torch.Tensor,
@@ -294,8 +304,15 @@ class Processor(nn.Module):
         -> [batch members M, .].  The first block's TransformerConv sees no noise and runs at ``batch``; its norm fans every row
         out into the members' rows; the later blocks run at ``batch members``."""
         edges_emb = self._edges(input_edge_attr)
-        first = self.cond_transformers[0]
         M = int(latent_mesh_nodes.shape[0]) // batch
+        if self.sparse:  # cond_norm_1 sees the noise before anything else: the rows fan out first, every block runs at batch members
+            ident = (None, torch.arange(M + 1, dtype=torch.int32, device=latent_mesh_nodes.device))
+            x = _LinearGatherGrouped.apply(None, None, None, ((None, M, members, ident),), batch * members, M,
+                                           _rows_in(latent_mesh_nodes, "latent_mesh_nodes"))
+            for cond_transformer in self.cond_transformers:
+                x = cond_transformer._forward_shared(x, edge_index, _rows_in(noise_vector, "noise_vector"), batch * members)
+            return x
+        first = self.cond_transformers[0]
         x = first.transformer_conv._forward_shared(latent_mesh_nodes, edge_index, edges_emb, batch)
         norm = first.cond_norm
         cond = _rows_in(noise_vector, "noise_vector")
@@ -363,7 +380,7 @@ class FunctionalGenerativeNetworkConfig:
     splits: int = 6
     num_hops: int = 6
     device: torch.device = torch.device("cpu")
-    sparse: bool = False
+    sparse: object = False  # False, True (the reference's DGL backend: raises) or "native"
     use_edges_features: bool = True
     scale_factor: float = 1.0
 
@@ -385,7 +402,7 @@ class FunctionalGenerativeNetwork(torch.nn.Module, PyTorchModelHubMixin):
 
     def __init__(self, grid_lon: np.ndarray, grid_lat: np.ndarray, input_features_dim: int, output_features_dim: int,
                  noise_dimension: int, hidden_dims: list[int] = [768, 768], num_blocks: int = 24, num_heads: int = 4, splits: int = 6,
-                 num_hops: int = 6, device: torch.device = torch.device("cpu"), sparse: bool = False, use_edges_features: bool = True,
+                 num_hops: int = 6, device: torch.device = torch.device("cpu"), sparse=False, use_edges_features: bool = True,
                  scale_factor: float = 1.0):
         super().__init__()
         self.num_lon = len(grid_lon)

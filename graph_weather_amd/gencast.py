@@ -1,6 +1,6 @@
 """The GenCast layers of the reference (``graph_weather/models/gencast/layers``): ``MLP``, ``InteractionNetwork``,
-``FourierEmbedding``, ``ConditionalLayerNorm``, ``CondTransformerBlock``, ``Encoder``, ``Processor`` (``sparse=False``) and
-``Decoder``.
+``FourierEmbedding``, ``ConditionalLayerNorm``, ``CondTransformerBlock``, ``Encoder``, ``Processor`` and ``Decoder``; the blocks of
+``Processor(sparse="native")`` are in ``gencast_sparse``.
 
 Same constructor arguments, defaults, argument checks, attribute names and ``state_dict`` keys (and their order) as the
 reference.  The reference builds on two ``torch_geometric`` classes; here ``TransformerConv`` is a parameter holder with PyG's
@@ -1098,13 +1098,33 @@ class Decoder(nn.Module):
         return self.grid_mlp_final(_Add.apply(_rows_in(input_grid_nodes, "input_grid_nodes"), update))
 
 
+def _sparse_mode(sparse) -> bool:
+    """The ``sparse`` argument of the processors: False - the ``TransformerConv`` blocks; "native" - the sparse blocks on this
+    package's kernels (True); anything else that is true asks for DGL, as the reference's ``sparse=True`` does."""
+    if isinstance(sparse, str) and sparse == "native":
+        return True
+    if sparse:
+        raise ValueError("Please install DGL to use sparsity. (sparse=\"native\" selects this package's own sparse processor.)")
+    return False
+
+
+def _sparse_blocks(blocks: nn.ModuleList, num_blocks: int, noise_emb_dim: int, latent_dim: int, num_heads: int, activation_layer) -> None:
+    from .gencast_sparse import SparseTransformer  # (that module builds on this one)
+
+    for _ in range(num_blocks):
+        blocks.append(SparseTransformer(conditioning_dim=noise_emb_dim, input_dim=latent_dim, output_dim=latent_dim,
+                                        num_heads=num_heads, activation_layer=activation_layer))
+
+
 class Processor(nn.Module):
-    """GenCast's processor (processor.py): transformer blocks over the mesh conditioned on the noise level.  ``sparse=True``
-    (the reference's DGL backend) is not provided."""
+    """GenCast's processor (processor.py): transformer blocks over the mesh conditioned on the noise level.  ``sparse="native"``
+    builds ``num_blocks`` ``gencast_sparse.SparseTransformer`` blocks (the reference's ``sparse=True`` processor on this package's
+    kernels; edge features are then ignored, as in the reference); ``sparse=True`` itself asks for the reference's DGL backend,
+    which is not installed here, and raises as the reference does without DGL."""
 
     def __init__(self, latent_dim: int, hidden_dims: list, num_blocks: int, num_heads: int, num_frequencies: int, base_period: int,
                  noise_emb_dim: int, edges_dim: Optional[int] = None, activation_layer: nn.Module = nn.ReLU,
-                 use_layer_norm: bool = True, sparse: bool = False):
+                 use_layer_norm: bool = True, sparse=False):
         super().__init__()
         self.latent_dim = latent_dim
         if latent_dim % num_heads != 0:
@@ -1115,8 +1135,10 @@ class Processor(nn.Module):
             self.edges_mlp = MLP(input_dim=edges_dim, hidden_dims=hidden_dims, activation_layer=activation_layer,
                                  use_layer_norm=use_layer_norm, bias=True, activate_final=False)
         self.cond_transformers = nn.ModuleList()
-        if sparse:
-            raise ValueError("Please install DGL to use sparsity.")
+        self.sparse = _sparse_mode(sparse)
+        if self.sparse:
+            _sparse_blocks(self.cond_transformers, num_blocks, noise_emb_dim, latent_dim, num_heads, activation_layer)
+            return
         e_dim = hidden_dims[-1] if (edges_dim is not None) else None
         for _ in range(num_blocks - 1):  # concatenating multi-head attention
             self.cond_transformers.append(CondTransformerBlock(conditioning_dim=noise_emb_dim, input_dim=latent_dim,
@@ -1162,5 +1184,8 @@ class Processor(nn.Module):
         noise_emb = self.fourier_embedder(noise_levels)
         edges_emb = self.edges_mlp(input_edge_attr) if self.edges_dim is not None else None
         for cond_transformer in self.cond_transformers:
-            latent_mesh_nodes = cond_transformer._forward_shared(latent_mesh_nodes, edge_index, edges_emb, noise_emb, batch)
+            if self.sparse:
+                latent_mesh_nodes = cond_transformer._forward_shared(latent_mesh_nodes, edge_index, noise_emb, batch)
+            else:
+                latent_mesh_nodes = cond_transformer._forward_shared(latent_mesh_nodes, edge_index, edges_emb, noise_emb, batch)
         return latent_mesh_nodes

@@ -16,7 +16,9 @@ batch-shared form of the layers (``gencast.Encoder._forward_shared`` and its sib
 
 Not reproduced: the reference's ``assert not torch.isnan(...)`` after every stage - each one is a host synchronisation.  The
 "strictly positive" check reads the device too; it is kept (with the reference's ``.any()``) but skipped while the current stream
-is capturing, so the eval forward can be captured in a ``torch.cuda.graph``.  fp32 only; ``sparse=True`` is not provided.
+is capturing, so the eval forward can be captured in a ``torch.cuda.graph``.  fp32 only.  ``sparse="native"`` (with
+``use_edges_features=False``) runs the processor on ``gencast_sparse.SparseTransformer`` blocks; ``sparse=True`` asks for the
+reference's DGL backend and raises as the reference does without DGL.
 """
 from __future__ import annotations
 
@@ -155,7 +157,7 @@ class DenoiserConfig:
     splits: int = 6
     num_hops: int = 6
     device: torch.device = torch.device("cpu")
-    sparse: bool = False
+    sparse: object = False  # False, True (the reference's DGL backend: raises) or "native"
     use_edges_features: bool = True
     scale_factor: float = 1.0
 
@@ -181,7 +183,7 @@ class Denoiser(torch.nn.Module, PyTorchModelHubMixin):
 
     def __init__(self, grid_lon: np.ndarray, grid_lat: np.ndarray, input_features_dim: int, output_features_dim: int,
                  hidden_dims: list[int] = [512, 512], num_blocks: int = 16, num_heads: int = 4, splits: int = 6, num_hops: int = 6,
-                 device: torch.device = torch.device("cpu"), sparse: bool = False, use_edges_features: bool = True,
+                 device: torch.device = torch.device("cpu"), sparse=False, use_edges_features: bool = True,
                  scale_factor: float = 1.0):
         super().__init__()
         self.num_lon = len(grid_lon)

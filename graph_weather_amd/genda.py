@@ -25,7 +25,9 @@ Deviations, on purpose:
     ``zeros_like`` temporaries are made, and mask and values receive zero gradients.
   * the reference's ``assert not torch.isnan(...)`` after every stage are host synchronisations and are not reproduced; the
     "strictly positive" check is kept (with the reference's ``.any()``) and skipped while the stream is capturing.
-  * ``wind_direction`` is accepted and ignored, as in the reference.  fp32 only; ``sparse=True`` is not provided.
+  * ``wind_direction`` is accepted and ignored, as in the reference.  fp32 only; ``sparse="native"`` (with
+    ``use_edges_features=False``) runs the processor on ``gencast_sparse.SparseTransformer`` blocks, ``sparse=True`` raises as the
+    reference does without DGL.
 """
 from __future__ import annotations
 
@@ -200,7 +202,7 @@ class GenDAConfig:
     splits: int = 6
     num_hops: int = 6
     device: torch.device = torch.device("cpu")
-    sparse: bool = False
+    sparse: object = False  # False, True (the reference's DGL backend: raises) or "native"
     use_edges_features: bool = True
     scale_factor: float = 1.0
 
@@ -224,7 +226,7 @@ class GenDA(torch.nn.Module, PyTorchModelHubMixin):
 
     def __init__(self, grid_lon: np.ndarray, grid_lat: np.ndarray, input_features_dim: int, output_features_dim: int,
                  hidden_dims: list[int] = [512, 512], num_blocks: int = 16, num_heads: int = 4, splits: int = 6, num_hops: int = 6,
-                 device: torch.device = torch.device("cpu"), sparse: bool = False, use_edges_features: bool = True,
+                 device: torch.device = torch.device("cpu"), sparse=False, use_edges_features: bool = True,
                  scale_factor: float = 1.0, conditioning_dim: int = 2):
         super().__init__()
         self.num_lon = len(grid_lon)

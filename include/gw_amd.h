@@ -1034,6 +1034,37 @@ int gw_genda_guided_output_backward(int32_t batch, int64_t grid_rows, int32_t wi
                                     const float* dout, int32_t ld_dout, float* dz, int32_t ld_dz, float* dpreds, int32_t ld_dpreds,
                                     void* stream);
 
+/* =====================================================================================================================
+ * GenCast's sparse processor (graph_weather/models/gencast/layers/experimental), csrc/gw_sparse_attn.hip: multi-head attention
+ * masked to a sparse [n_rows, n_cols] matrix, no edge term, no head mean.  fp32, plain stores, no atomics, every sum in one fixed
+ * order (bitwise reproducible), no host synchronisation; 0 rows or 0 entries: GW_OK without a launch (the caller zero-fills).
+ *
+ * The mask is a row-sorted CSR: the entries [row_ptr[i], row_ptr[i + 1]) belong to attending row i, entry t attends column col[t];
+ * every entry is its own term (a duplicate counts twice).  Rows are in the head-major layout: head h of `heads` is the contiguous
+ * segment [h dim_head, (h + 1) dim_head) of a row; heads * dim_head <= 4096 (GW_E_UNSUPPORTED above).  Per head
+ *   s_t = (scale q[i, h]) . k[col[t], h],  p = softmax of s over the entries of row i,  out[i, h] = sum_t p_t v[col[t], h];
+ * a row without entries gets 0.  q, out [batch n_rows, heads dim_head] and k, v [batch n_cols, heads dim_head], each with its own
+ * leading dimension (column blocks of one stacked projection are read in place): `batch` >= 1 copies of the mask share the plan,
+ * copy b's rows start at b n_rows resp. b n_cols (64-bit offsets).  lse [2, batch n_rows heads]: plane 0 the maximum of the scores
+ * of (row, head), plane 1 log sum_t exp(s_t - max); both 0 for a row without entries.  One wave per (copy, row) covers all heads
+ * with an online softmax: nothing of size n_edges x heads x dim_head or n_edges x heads is written.  Register path (16-byte loads,
+ * a 64 / heads lane group per head): heads divides 64, dim_head a multiple of 4, heads * dim_head <= 2048, every leading dimension a
+ * multiple of 4 and 16-byte aligned tables; anything else runs a general path (one wave per row, the heads in order).
+ *
+ * gw_sparse_attention_backward recomputes the probabilities from q, k and lse.  out: the forward's rows; dout like out.  One launch
+ * over rows writes delta [batch n_rows heads] (scratch the caller provides) and dq (the gradient of the UNSCALED q); one launch over
+ * columns walks col_pos / col_ptr (row-sorted positions grouped by column; row[t] = row of sorted entry t) and writes dk and dv.
+ * Every row of dq, dk, dv is written once. */
+int gw_sparse_attention_forward(int32_t batch, int32_t n_rows, int32_t n_cols, int32_t n_edges, int32_t heads, int32_t dim_head,
+                                float scale, const int32_t* row_ptr, const int32_t* col, const float* q, int32_t ld_q, const float* k,
+                                int32_t ld_k, const float* v, int32_t ld_v, float* out, int32_t ld_out, float* lse, void* stream);
+int gw_sparse_attention_backward(int32_t batch, int32_t n_rows, int32_t n_cols, int32_t n_edges, int32_t heads, int32_t dim_head,
+                                 float scale, const int32_t* row_ptr, const int32_t* col, const int32_t* row, const int32_t* col_pos,
+                                 const int32_t* col_ptr, const float* q, int32_t ld_q, const float* k, int32_t ld_k, const float* v,
+                                 int32_t ld_v, const float* out, int32_t ld_out, const float* dout, int32_t ld_dout, const float* lse,
+                                 float* delta, float* dq, int32_t ld_dq, float* dk, int32_t ld_dk, float* dv, int32_t ld_dv,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
