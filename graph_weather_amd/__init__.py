@@ -58,6 +58,11 @@ from . import gencast_graphs, gencast_model  # noqa: F401  (GenCast's GraphBuild
 from . import gencast_sparse  # noqa: F401  (GenCast's sparse processor blocks: the masked attention of csrc/gw_sparse_attn.hip)
 from . import gencast_sampler  # noqa: F401  (GenCast's Sampler and WeightedMSELoss; the inverse transform of csrc/gw_sht.hip draws the noise)
 from .gencast_sampler import Sampler, WeightedMSELoss  # noqa: F401
+from .weathermesh import (  # noqa: F401  (WeatherMesh's processor: the 3-D neighbourhood attention of csrc/gw_na3d.hip)
+    NeighborhoodAttention3D,
+    WeatherMeshProcessor,
+    WeatherMeshProcessorConfig,
+)
 from .graphed import ForwardGraph  # noqa: F401  (the inference forward as one HIP graph)
 from .rollout import rollout  # noqa: F401
 from .optim import AdamW  # noqa: F401

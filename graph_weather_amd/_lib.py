@@ -62,6 +62,7 @@ EXPORTS = [
     "gw_ensemble_crps_workspace_bytes", "gw_ensemble_crps_forward", "gw_ensemble_crps_backward",
     "gw_genda_input_forward", "gw_genda_input_backward", "gw_genda_guided_output_forward", "gw_genda_guided_output_backward",
     "gw_sparse_attention_forward", "gw_sparse_attention_backward",
+    "gw_na3d_forward", "gw_na3d_backward",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -519,6 +520,11 @@ def lib():
     L.gw_sparse_attention_backward.restype = c_int
     L.gw_sparse_attention_backward.argtypes = [c_int32] * 6 + [c_float] + [c_void_p] * 5 + [c_void_p, c_int32] * 5 + [
         c_void_p, c_void_p] + [c_void_p, c_int32] * 3 + [c_void_p]
+    L.gw_na3d_forward.restype = c_int
+    L.gw_na3d_forward.argtypes = [c_int32] * 9 + [c_float] + [c_void_p, c_int32] * 4 + [c_void_p, c_void_p]
+    L.gw_na3d_backward.restype = c_int
+    L.gw_na3d_backward.argtypes = [c_int32] * 9 + [c_float] + [c_void_p, c_int32] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int32] * 3 + [
+        c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

@@ -1065,6 +1065,36 @@ int gw_sparse_attention_backward(int32_t batch, int32_t n_rows, int32_t n_cols, 
                                  float* delta, float* dq, int32_t ld_dq, float* dk, int32_t ld_dk, float* dv, int32_t ld_dv,
                                  void* stream);
 
+/* =====================================================================================================================
+ * WeatherMesh's processor (graph_weather/models/weathermesh/processor.py), csrc/gw_na3d.hip: 3-D neighbourhood attention as
+ * NATTEN's NeighborhoodAttention3D documents it (restated, not pinned against NATTEN): non-causal, stride 1, dilation 1, no
+ * position bias.  fp32, plain stores, no atomics, every sum in one fixed order (bitwise reproducible), no host synchronisation;
+ * batch 0: GW_OK without a launch.
+ *
+ * Tokens are the rows of a [batch, depth, height, width] volume in that order, heads * dim_head floats per row, head h the
+ * contiguous segment [h dim_head, (h + 1) dim_head).  Per axis of length L with kernel k (odd, 1 <= k <= L, GW_E_BADARG else)
+ * the query at index i attends to the k indices from clamp(i - k / 2, 0, L - k): windows shift inward at a border and keep k
+ * keys.  Per head s = scale q . k over the kd kh kw keys of the product of the three ranges, p = softmax(s), out = sum p v.
+ * q, k, v, out each have their own leading dimension (column blocks of one stacked projection are read in place); volume offsets
+ * are 64-bit, batch depth height width heads < 2^31.  lse [2, rows heads]: plane 0 the maximum of the scores of (row, head),
+ * plane 1 log sum exp(s - max).  dim_head <= 256 (GW_E_UNSUPPORTED above).
+ *
+ * Tiled path (dim_head a multiple of 4 and <= 64, kh and kw <= 7, leading dimensions multiples of 4, 16-byte aligned tables, the
+ * staged planes within 160 KB of LDS): a workgroup owns 8 x 8 queries of one depth plane and one head and stages the union of
+ * their windows once per key plane; the softmax is online across window rows and planes.  Anything else runs a general path (one
+ * wave per token, the heads in order, everything streamed).
+ *
+ * gw_na3d_backward recomputes the probabilities from q, k and lse.  out: the forward's rows; dout like out.  A query-side launch
+ * writes delta [rows heads] (scratch the caller provides) and dq (the gradient of the UNSCALED q); a key-side launch walks, per
+ * key, the box of queries that attend to it and writes dk and dv.  Every row of dq, dk, dv is written once. */
+int gw_na3d_forward(int32_t batch, int32_t depth, int32_t height, int32_t width, int32_t heads, int32_t dim_head, int32_t kd, int32_t kh,
+                    int32_t kw, float scale, const float* q, int32_t ld_q, const float* k, int32_t ld_k, const float* v, int32_t ld_v,
+                    float* out, int32_t ld_out, float* lse, void* stream);
+int gw_na3d_backward(int32_t batch, int32_t depth, int32_t height, int32_t width, int32_t heads, int32_t dim_head, int32_t kd, int32_t kh,
+                     int32_t kw, float scale, const float* q, int32_t ld_q, const float* k, int32_t ld_k, const float* v, int32_t ld_v,
+                     const float* out, int32_t ld_out, const float* dout, int32_t ld_dout, const float* lse, float* delta, float* dq,
+                     int32_t ld_dq, float* dk, int32_t ld_dk, float* dv, int32_t ld_dv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
