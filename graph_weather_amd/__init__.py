@@ -63,6 +63,17 @@ from .weathermesh import (  # noqa: F401  (WeatherMesh's processor: the 3-D neig
     WeatherMeshProcessor,
     WeatherMeshProcessorConfig,
 )
+from .weathermesh_model import (  # noqa: F401  (WeatherMesh's conv towers, encoder, decoder and model: csrc/gw_convnd.hip)
+    ConvDownBlock,
+    ConvUpBlock,
+    WeatherMesh,
+    WeatherMeshConfig,
+    WeatherMeshDecoder,
+    WeatherMeshDecoderConfig,
+    WeatherMeshEncoder,
+    WeatherMeshEncoderConfig,
+    WeatherMeshOutput,
+)
 from .graphed import ForwardGraph  # noqa: F401  (the inference forward as one HIP graph)
 from .rollout import rollout  # noqa: F401
 from .optim import AdamW  # noqa: F401

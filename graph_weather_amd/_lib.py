@@ -63,6 +63,8 @@ EXPORTS = [
     "gw_genda_input_forward", "gw_genda_input_backward", "gw_genda_guided_output_forward", "gw_genda_guided_output_backward",
     "gw_sparse_attention_forward", "gw_sparse_attention_backward",
     "gw_na3d_forward", "gw_na3d_backward",
+    "gw_convnd_workspace_bytes", "gw_convnd_forward", "gw_convnd_dgrad", "gw_convnd_wgrad", "gw_convnd_bn_stats",
+    "gw_convnd_tail_forward", "gw_convnd_tail_backward", "gw_convnd_upsample2x",
 ]
 
 GEMM_NN, GEMM_TN, GEMM_TN_BF16X3 = 0, 1, 2
@@ -101,6 +103,7 @@ class GwConstraintArgs(Structure):  # include/gw_amd.h: gw_constraint_args
 ACT_NONE, ACT_RELU, ACT_SILU = 0, 1, 2  # GW_ACT_*
 CRPS_MEAN, CRPS_NONE = 0, 1  # GW_CRPS_*
 
+CONVND_A_PLAIN, CONVND_A_BN_GELU = 0, 1  # GW_CONVND_A_*
 THERMAL_MAX_TAPS = 7  # GW_THERMAL_MAX_TAPS
 THERMAL_A_PLAIN, THERMAL_A_GN_RELU, THERMAL_A_DIFFUSE = 0, 1, 2  # GW_THERMAL_A_*
 THERMAL_E_STORE, THERMAL_E_DIFFUSE = 0, 1  # GW_THERMAL_E_*
@@ -525,6 +528,27 @@ def lib():
     L.gw_na3d_backward.restype = c_int
     L.gw_na3d_backward.argtypes = [c_int32] * 9 + [c_float] + [c_void_p, c_int32] * 5 + [c_void_p, c_void_p] + [c_void_p, c_int32] * 3 + [
         c_void_p]
+    i64p, i32p = POINTER(c_int64), POINTER(c_int32)
+    L.gw_convnd_workspace_bytes.restype = c_size_t
+    L.gw_convnd_workspace_bytes.argtypes = [i32p]
+    L.gw_convnd_forward.restype = c_int
+    L.gw_convnd_forward.argtypes = [i32p, c_int32, c_void_p, i64p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i64p, c_void_p]
+    L.gw_convnd_dgrad.restype = c_int
+    L.gw_convnd_dgrad.argtypes = [i32p, c_void_p, i64p, c_void_p, c_void_p, i64p, c_int32, c_void_p]
+    L.gw_convnd_wgrad.restype = c_int
+    L.gw_convnd_wgrad.argtypes = [i32p, c_int32, c_void_p, i64p, c_void_p, c_void_p, c_void_p, i64p, c_void_p, c_size_t, c_void_p,
+                                  c_void_p, c_void_p]
+    L.gw_convnd_bn_stats.restype = c_int
+    L.gw_convnd_bn_stats.argtypes = [c_int32, c_int32, c_int64, c_int32, c_void_p, i64p, c_void_p, c_void_p, c_float, c_float,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]
+    L.gw_convnd_tail_forward.restype = c_int
+    L.gw_convnd_tail_forward.argtypes = [c_int32, c_int32, c_int64, c_void_p, i64p, c_void_p, c_void_p, i64p, c_void_p, c_void_p, i64p,
+                                         c_void_p]
+    L.gw_convnd_tail_backward.restype = c_int
+    L.gw_convnd_tail_backward.argtypes = [c_int32, c_int32, c_int64, c_int32, c_void_p, i64p, c_void_p, i64p, c_void_p, c_void_p, i64p,
+                                          c_void_p, c_void_p, c_void_p, i64p, c_void_p, i64p, c_void_p]
+    L.gw_convnd_upsample2x.restype = c_int
+    L.gw_convnd_upsample2x.argtypes = [c_int32] * 6 + [c_void_p, i64p, c_void_p, i64p, c_void_p]
     if L.gw_version() != ABI_VERSION:
         raise RuntimeError("graph_weather_amd: libgw_amd.so ABI version mismatch")
     _lib = L

@@ -838,6 +838,52 @@ int gw_conv3d_backward(int32_t batch, int32_t cin, int32_t cout, int32_t d, int3
                        const int64_t* stride_x, const float* weight, const float* dout, const int64_t* stride_dout, void* workspace,
                        size_t workspace_bytes, float* dx, const int64_t* stride_dx, float* dweight, float* dbias, void* stream);
 
+/* The convolution towers of WeatherMesh (csrc/gw_convnd.hip; graph_weather/models/weathermesh/layers.py): convolutions with
+ * kernel 1 or 3, padding k / 2 and stride 1 or 2 per axis, BatchNorm statistics, the residual tail gelu(bn2(y2) + bn_skip(ys)) and
+ * 2 x bilinear upsampling.  fp32, no atomics, every launch bitwise repeatable.  Volumes are addressed by three strides as above.
+ *
+ * geo[12] = batch, cin, cout, d, h, w (of the convolution's INPUT), kd, kh, kw (1 or 3), sd, sh, sw (1 or 2); the output has
+ * (L - 1) / s + 1 voxels per axis; a 2-D convolution is d = kd = sd = 1.  weight [cout, cin, kd, kh, kw] contiguous.
+ *   gw_convnd_forward   out = bias + conv(A(x)); a_mode PLAIN: A(x) = x; BN_GELU: A(x) = gelu(x a_scale[c] + a_shift[c]) (exact
+ *                       erf form), applied on load before the zero padding; bias [cout] may be NULL.
+ *   gw_convnd_dgrad     dx (the input's layout) = the data gradient of dout (the output's), one launch per parity class of the
+ *                       strided axes with that class's own taps; accumulate != 0: dx += it.
+ *   gw_convnd_wgrad     dweight and dbias (may be NULL) from A(x) and dout: partials per slab of 1024 output voxels in
+ *                       gw_convnd_workspace_bytes (host-side query, 0 with the error set on bad arguments), added in slab order.
+ * gw_convnd_bn_stats: the table stats [4][channels] = scale (gamma rstd), shift (beta - mean scale), mean, rstd of a BatchNorm
+ *   over (batch, voxels) of x.  training != 0: batch mean and biased variance (two passes, one workgroup per channel) and, when
+ *   the running buffers are given, running = (1 - momentum) running + momentum (mean | unbiased variance); training == 0: mean and
+ *   variance are the running buffers' and x is not read.
+ * gw_convnd_tail_forward: out = gelu(y2 scale2 + shift2 + ys scales + shifts) from the tables st2 and sts; ys NULL: one term.
+ * gw_convnd_tail_backward: dz = dout gelu'(.) is recomputed; one reduction launch writes sums [4][channels] = sum dz, sum dz zhat2,
+ *   sum dz, sum dz zhats (d beta and d gamma of the two norms; rows 0 and 1 only when ys is NULL), one apply launch writes
+ *   dy2 = scale2 (dz - mean dz - zhat2 mean(dz zhat2)) (training) or scale2 dz (training == 0), and dys likewise.
+ * gw_convnd_upsample2x: F.interpolate(scale_factor = (1, 2, 2), align_corners = False) of x [batch, channels, d, h, w] into out
+ *   [.., d, 2 h, 2 w]; backward != 0: x is the gradient of the upsampled volume, out the source's (gather form). */
+#define GW_CONVND_A_PLAIN 0
+#define GW_CONVND_A_BN_GELU 1
+size_t gw_convnd_workspace_bytes(const int32_t* geo);
+int gw_convnd_forward(const int32_t* geo, int32_t a_mode, const float* x, const int64_t* stride_x, const float* a_scale,
+                      const float* a_shift, const float* weight, const float* bias, float* out, const int64_t* stride_out,
+                      void* stream);
+int gw_convnd_dgrad(const int32_t* geo, const float* dout, const int64_t* stride_dout, const float* weight, float* dx,
+                    const int64_t* stride_dx, int32_t accumulate, void* stream);
+int gw_convnd_wgrad(const int32_t* geo, int32_t a_mode, const float* x, const int64_t* stride_x, const float* a_scale,
+                    const float* a_shift, const float* dout, const int64_t* stride_dout, void* workspace, size_t workspace_bytes,
+                    float* dweight, float* dbias, void* stream);
+int gw_convnd_bn_stats(int32_t batch, int32_t channels, int64_t voxels, int32_t training, const float* x, const int64_t* stride_x,
+                       const float* gamma, const float* beta, float eps, float momentum, float* running_mean, float* running_var,
+                       float* stats, void* stream);
+int gw_convnd_tail_forward(int32_t batch, int32_t channels, int64_t voxels, const float* y2, const int64_t* stride_y2, const float* st2,
+                           const float* ys, const int64_t* stride_ys, const float* sts, float* out, const int64_t* stride_out,
+                           void* stream);
+int gw_convnd_tail_backward(int32_t batch, int32_t channels, int64_t voxels, int32_t training, const float* dout,
+                            const int64_t* stride_dout, const float* y2, const int64_t* stride_y2, const float* st2, const float* ys,
+                            const int64_t* stride_ys, const float* sts, float* sums, float* dy2, const int64_t* stride_dy2, float* dys,
+                            const int64_t* stride_dys, void* stream);
+int gw_convnd_upsample2x(int32_t batch, int32_t channels, int32_t d, int32_t h, int32_t w, int32_t backward, const float* x,
+                         const int64_t* stride_x, float* out, const int64_t* stride_out, void* stream);
+
 /* =====================================================================================================================
  * GenCast layers (graph_weather/models/gencast/layers), csrc/gw_gencast.hip: graph-transformer attention (the TransformerConv
  * of the mesh processor) and the row operations around it.  All fp32, no atomics, every sum in one fixed order (bitwise
